@@ -22,6 +22,11 @@ runs the per-tick exchange (all-gather of per-row counts, MAX-allreduce of
 resolved gossip draws) with RCCL on its own stream; torch.distributed is only
 the CPU (gloo) rendezvous that hands every rank the RCCL unique id, plus the
 barrier / max-over-ranks timing. See DESIGN.md §Multi-GPU.
+
+A plain run sets up, warms up, times the K ticks, checks the workload and prints
+the line (--dump-outputs DIR also writes a seeded sample of the last tick's state
+as .npy files). --full adds the legs that are runs of their own: the cpu_baseline,
+the S-B companion run and the live PMC traffic passes.
 """
 import argparse
 import json
@@ -79,20 +84,31 @@ def parse():
     p.add_argument("--crash-tick", type=int, default=10)
     p.add_argument("--crash-frac", type=float, default=0.01)
     p.add_argument("--cpu-seconds", type=float, default=12.0)
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     p.add_argument("--drop-pct", type=int, default=0,
                    help="diagnostics (S-A): keyed per-entry drops on every tick (the drop path of gm_s_band)")
     p.add_argument("--force-shard", action="store_true",
                    help="diagnostics: at N=1 run the column-shard protocol with RCCL over one rank")
     p.add_argument("--no-companion", dest="companion", action="store_false",
-                   help="S-A only: skip the companion S-B run (N=262,144, same schedule and ranks) whose line "
-                        "goes under \"companion\" -- the north_star scaling cluster measured by every --gpus G run")
+                   help="--full, S-A only: skip the companion S-B run (N=262,144, same schedule and ranks) whose line "
+                        "goes under \"companion\" -- the north_star scaling cluster measured by every --full --gpus G run")
     p.add_argument("--no-pmc", dest="pmc", action="store_false",
-                   help="skip the live traffic measurement: by default (N=1) roofline.traffic is measured after "
+                   help="--full: skip the live traffic measurement: under --full (N=1) roofline.traffic is measured after "
                         "the timed run by two rocprofv3 --pmc passes of this workload (FETCH_SIZE, WRITE_SIZE; as "
                         "scripts/gpu.sh pmc_sa / pmc_sc), falling back to the committed profiles/traffic_*.json")
     p.add_argument("--pmc", dest="pmc", action="store_true", help=argparse.SUPPRESS)  # the default; kept for old callers
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline run also measure what takes runs of its own: the cpu_baseline leg "
+                        "(--no-cpu skips it), the S-B companion run (--no-companion) and the live PMC traffic passes "
+                        "(--no-pmc). Without --full a run sets up, warms up, times the K steps and prints its line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed tick left as DIR/<name>.npy (float32 / "
+                        "float64): a fixed seeded sample of table rows (S-A, S-B) or views (S-C), the node states, "
+                        "the last gossip draws and the tick / event counters; < 64 MB")
+    a = p.parse_args()
+    if not a.full:  # a plain run: only what the headline figure needs
+        a.companion, a.pmc, a.no_cpu = False, False, True
+    return a
 
 
 def live_traffic(kernel, layout, n, extra):
@@ -103,7 +119,7 @@ def live_traffic(kernel, layout, n, extra):
     import subprocess
     import tempfile
     d = tempfile.mkdtemp(prefix="gm_pmc_", dir=os.environ.get("TMPDIR", "/tmp"))
-    child = [sys.executable, os.path.abspath(__file__), "--no-cpu", "--no-pmc", "--steps", "5", "--warmup", "1"] + extra
+    child = [sys.executable, os.path.abspath(__file__), "--steps", "5", "--warmup", "1"] + extra  # plain runs
     for ctr, sub in (("FETCH_SIZE", "fetch"), ("WRITE_SIZE", "write")):
         cmd = ["rocprofv3", "--pmc", ctr, "--kernel-trace", "--output-format", "csv", "-d", os.path.join(d, sub),
                "-o", "p", "--"] + child
@@ -115,6 +131,77 @@ def live_traffic(kernel, layout, n, extra):
     with open(out) as f:
         tj = json.load(f)
     return tj["hbm_bytes_per_launch"], f"live: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload ({d})"
+
+
+def sample_indices(n, count, seed):
+    """A fixed, seeded sample of min(count, n) distinct indices in [0, n), ascending (a splitmix64
+    stream, so the sample depends on nothing but its arguments)."""
+    if count >= n:
+        return list(range(n))
+    m64 = (1 << 64) - 1
+    x, out = seed & m64, set()
+    while len(out) < count:
+        x = (x + 0x9E3779B97F4A7C15) & m64
+        z = x
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m64
+        out.add((z ^ (z >> 31)) % n)
+    return sorted(out)
+
+
+def save_outputs(a, rank, world, arrays):
+    """--dump-outputs: DIR/<name>.npy (a rank of a --gpus G > 1 run writes <name>_rank<r>.npy)"""
+    import numpy as np
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    total = 0
+    for name, arr in arrays.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        total += arr.nbytes
+        np.save(os.path.join(a.dump_outputs, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), arr)
+    assert total <= 64 << 20, total
+
+
+DUMP_SEED = 2024
+
+
+def dump_scaled(a, sim, rank, world, W):
+    """What the last timed SCALED tick left, as a caller of the C ABI reads it back: (hb, ts) of
+    a seeded sample of observer rows over this rank's W subject columns (gm_read_row, -1 =
+    absent; every value < 2^15, exact in float32), every node's state (gm_read_nodes), the
+    tick's gossip draws (gm_read_targets, one GPU) and the tick / event counters."""
+    import numpy as np
+    n = sim.n
+    rows = sample_indices(n, max(1, min(48, (20 << 20) // (4 * W))), DUMP_SEED)
+    hb = np.empty((len(rows), W), dtype=np.float32)
+    ts = np.empty((len(rows), W), dtype=np.float32)
+    for k, r in enumerate(rows):
+        hb[k], ts[k] = sim.read_row(r, 0, W)
+    st, tot = sim.tick_stats(), sim.event_totals()
+    arrays = {"table_rows": np.asarray(rows, dtype=np.float64), "table_hb": hb, "table_ts": ts,
+              "nodes": sim.read_nodes().astype(np.float32),
+              "tick_stats": np.asarray([st["lists"], st["live"], st["max_inbox"], st["err"]], dtype=np.float64),
+              "event_totals": np.asarray([tot["total"], tot["joined"], tot["removed"]], dtype=np.float64)}
+    if world == 1 and not a.force_shard:
+        tg, cnt = sim.read_targets()
+        arrays["targets"], arrays["target_counts"] = tg.astype(np.float32), cnt.astype(np.float32)
+    save_outputs(a, rank, world, arrays)
+
+
+def dump_partial(a, sim, rank, world):
+    """What the last timed PARTIAL tick left: the views (gm_read_views; id and heartbeat of
+    every entry, 0 = empty slot) of a seeded sample of 1,024-node chunks of this rank's
+    nodes, and the tick counters."""
+    import numpy as np
+    n0, nloc = sim.shard_layout()
+    chunk = min(1024, nloc)
+    starts = [n0 + c * chunk for c in sample_indices(nloc // chunk, 32, DUMP_SEED)]
+    views = np.concatenate([sim.read_views(s, chunk) for s in starts])
+    st = sim.tick_stats()
+    save_outputs(a, rank, world, {
+        "view_nodes": np.concatenate([np.arange(s, s + chunk) for s in starts]).astype(np.float64),
+        "view_id": (views >> np.uint64(32)).astype(np.float64),
+        "view_hb": (views & np.uint64(0xFFFFFFFF)).astype(np.float64),
+        "tick_stats": np.asarray([st["lists"], st["live"], st["max_inbox"], st["err"]], dtype=np.float64)})
 
 
 _JSON_FD = None
@@ -430,13 +517,15 @@ def main():
         "check": {"removed_rank0": tot["removed"], "joined_rank0": tot["joined"], "removed_all_expected":
                   (n - ncrash) * ncrash if removed_ok else None},
     }
+    if a.dump_outputs:
+        dump_scaled(a, sim, rank, world, W)
     sim.close()  # the companion run and the PMC passes (child processes) need the device memory
     if a.companion and a.scenario == "S-A" and n == 65536 and not a.drop_pct and not a.force_shard:
         out["companion"] = companion_sb(a, rank, world, local, dist, rtx)
     if a.pmc and world == 1:
         try:
             out["roofline"]["traffic"], out["roofline"]["traffic_source"] = live_traffic(
-                "gm_s_band", LAYOUT_SA, n, ["--cluster", str(n), "--no-companion"] +
+                "gm_s_band", LAYOUT_SA, n, ["--cluster", str(n)] +
                 (["--drop-pct", str(a.drop_pct)] if a.drop_pct else []))
         except Exception as e:  # no profiler / counters on this host: the committed figure stands, said so
             out["roofline"]["traffic_source"] = f"{traffic_src} (live PMC passes failed: {type(e).__name__})"
@@ -611,6 +700,8 @@ def main_partial(a):
     }
     if world > 1:
         out["roofline"]["note"] = "rank 0's local kernels (its n/G nodes)"
+    if a.dump_outputs:
+        dump_partial(a, sim, rank, world)
     if a.pmc and world == 1:
         sim.close()  # the PMC passes are child processes with their own context
         try:

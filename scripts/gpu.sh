@@ -4,11 +4,11 @@
 #
 #   tests      python -m pytest tests -m gpu            -> $O/gpu_tests.txt
 #   smoke      __graft_entry__.smoke()                  -> $O/smoke.txt
-#   sa         bench.py (S-A, with cpu_baseline, live PMC traffic and the S-B companion run) -> $O/bench_sa.json
-#   sc         bench.py --scenario S-C                  -> $O/bench_sc.json
+#   sa         bench.py --full (S-A, with cpu_baseline, live PMC traffic and the S-B companion run) -> $O/bench_sa.json
+#   sc         bench.py --full --scenario S-C             -> $O/bench_sc.json
 #   ticks      scripts/tick_times.py: per-tick gm_s_band time of the S-A schedule -> $O/tick_times.txt
-#   sb         bench.py --cluster 262144 (S-B on one GPU) -> $O/bench_sb.json
-#   sa_pmc     bench.py --pmc (S-A, traffic measured live by two child PMC passes) -> $O/bench_sa_pmc.json
+#   sb         bench.py --full --cluster 262144 (S-B on one GPU) -> $O/bench_sb.json
+#   sa_pmc     bench.py --full --no-cpu (S-A, traffic measured live by two child PMC passes) -> $O/bench_sa_pmc.json
 #   shard      bench.py --force-shard (RCCL, 1 rank)    -> $O/bench_force_shard.json
 #   sbshard    scripts/shard_profile.py --sb            -> $O/sb_shard.json
 #   prof_sa    rocprofv3 --kernel-trace --stats of S-A  -> $O/prof_sa/
@@ -36,11 +36,11 @@ run_step() {
   case "$1" in
     tests) timeout -k 10 1400 $PT ${TESTS:-tests} -m gpu --durations 15 > $O/gpu_tests.txt 2>&1 ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 ;;
-    sa) timeout -k 10 300 python -u bench.py ${BENCH_ARGS:-} > $O/bench_sa.json 2> $O/bench_sa.err ;;
-    sc) timeout -k 10 400 python -u bench.py --scenario S-C ${BENCH_ARGS:-} > $O/bench_sc.json 2> $O/bench_sc.err ;;
+    sa) timeout -k 10 300 python -u bench.py --full ${BENCH_ARGS:-} > $O/bench_sa.json 2> $O/bench_sa.err ;;
+    sc) timeout -k 10 400 python -u bench.py --full --scenario S-C ${BENCH_ARGS:-} > $O/bench_sc.json 2> $O/bench_sc.err ;;
     ticks) timeout -k 10 300 python -u scripts/tick_times.py ${TICKS_N:-65536} > $O/tick_times.txt 2>&1 ;;
-    sb) timeout -k 10 400 python -u bench.py --cluster 262144 ${BENCH_ARGS:-} > $O/bench_sb.json 2> $O/bench_sb.err ;;
-    sa_pmc) timeout -k 10 700 python -u bench.py --pmc --no-cpu ${BENCH_ARGS:-} > $O/bench_sa_pmc.json 2> $O/bench_sa_pmc.err ;;
+    sb) timeout -k 10 400 python -u bench.py --full --cluster 262144 ${BENCH_ARGS:-} > $O/bench_sb.json 2> $O/bench_sb.err ;;
+    sa_pmc) timeout -k 10 700 python -u bench.py --full --pmc --no-cpu ${BENCH_ARGS:-} > $O/bench_sa_pmc.json 2> $O/bench_sa_pmc.err ;;
     shard) timeout -k 10 300 python -u bench.py --force-shard --no-cpu --no-pmc --no-companion ${BENCH_ARGS:-} > $O/bench_force_shard.json 2> $O/bench_force_shard.err ;;
     sbshard) timeout -k 10 400 python -u scripts/shard_profile.py --sb > $O/sb_shard.json 2> $O/sb_shard.err ;;
     prof_sa) timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_sa -o sa -- \

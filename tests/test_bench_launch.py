@@ -24,7 +24,7 @@ def _run(args, **extra):
 
 
 def test_gpus_2_spawns_two_ranks():
-    r = _run(["--gpus", "2", "--dry-launch"])
+    r = _run(["--gpus", "2", "--dry-launch", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout  # rank 0 alone prints ONE JSON line
@@ -36,7 +36,7 @@ def test_gpus_2_spawns_two_ranks():
     assert sorted(x["local_rank"] for x in ranks) == [0, 1]
     assert len({x["pid"] for x in ranks}) == 2  # two processes
     assert all(x["master"].startswith("127.0.0.1:") for x in ranks)
-    assert out["companion"] == "S-B"  # every S-A line of a --gpus sweep also measures the S-B cluster
+    assert out["companion"] == "S-B"  # every --full S-A line of a --gpus sweep also measures the S-B cluster
 
 
 def test_gpus_1_stays_one_process():
@@ -50,7 +50,13 @@ def test_gpus_1_stays_one_process():
 
 
 def test_no_companion_flag():
-    r = _run(["--dry-launch", "--no-companion"])
+    r = _run(["--dry-launch", "--full", "--no-companion"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip())["companion"] is None
+
+
+def test_plain_run_has_no_companion():
+    r = _run(["--dry-launch"])  # the companion run belongs to --full
     assert r.returncode == 0, r.stderr[-2000:]
     assert json.loads(r.stdout.strip())["companion"] is None
 

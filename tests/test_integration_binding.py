@@ -19,10 +19,8 @@ REF = "/root/reference"
 SRC = os.path.join(REPO, "tests", "integration", "Application_gm.cpp")
 LIB = os.path.join(REPO, "distributed-membership_amd", "lib")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF) or not shutil.which("g++"),
-                                reason="the reference sources are in the build container only")
-
-
+@pytest.mark.skipif(not os.path.isdir(REF) or not shutil.which("g++"),
+                    reason="the reference sources are in the build container only")
 def test_binding_compiles_against_reference_headers_and_links_libgm(tmp_path):
     if not os.path.exists(os.path.join(LIB, "libgm.so")):
         pytest.skip("libgm.so not built")
