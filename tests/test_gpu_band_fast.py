@@ -4,8 +4,12 @@ tick by tick: events in order, tick statistics, membership tables, msgcount. The
 every branch of the fast path: the crash window (cells aging to 15 escape, then TREMOVE removes
 them: the per-cell pass, the quick case of a slice whose escapes only age, and the removal events), cold start (every cell escaped: escape lists read
 back), a loss window (DROP ticks take the general kernel; the ticks after it deliver stale and
-lagging entries, so units are handed back to the general path), and column shards. The oracle
-parity of both paths is test_gpu_scaled.py's (bands 1024 included). Reference: the merge
+lagging entries, so units are handed back to the general path), and column shards. At an odd and
+a padded band count (nb = 3, nb = 4) a third context runs the general band and pick kernels
+together (GM_BAND_FAST=0, GM_PICK0=0) and the gossip draws are compared too. The oracle parity of
+both paths at one band is test_gpu_scaled.py's (bands 1024 included); at more bands it is
+test_gpu_multiband.py's: oracle windows on the production path at nb = 2 and 3, and
+gm_s_pick0 == gm_s_pick at nb = 17 (a two-level band search). Reference: the merge
 MP1Node.cpp:278-299, the sweep MP1Node.cpp:426-444, sendMemberList MP1Node.cpp:360-395."""
 import numpy as np
 import pytest
@@ -60,6 +64,54 @@ def test_fast_path_matches_general_path(monkeypatch, init_mode, loss, ncrash):
             _same_tables(gen, fast, n, t)
         (sg, rg), (sf, rf) = gen.msgcount(t), fast.msgcount(t)
         assert np.array_equal(sg, sf) and np.array_equal(rg, rf), f"msgcount differs at tick {t}"
+    assert fast.tick_stats()["err"] == 0
+
+
+def _same_arrays(a, b):
+    return all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("init_mode,loss,crash_pct", [(1, 0, 1), (0, 2, 2)])
+@pytest.mark.parametrize("n", [2564, 3586])
+def test_fast_path_matches_general_kernels_odd_and_padded_bands(monkeypatch, n, init_mode, loss, crash_pct):
+    # nb = 3 (N = 2564: per row one two-band wave and a single-band tail wave; 516 real columns in the
+    # last band) and nb = 4 (N = 3586: 514 real columns in the last band, N % 4 = 2 -- rows pad to a
+    # multiple of 512 columns, so no 1024-band region has a last band of fewer than 513). Three contexts:
+    # the production path (gm_s_band_fast + gm_s_pick0), the general band kernel with gm_s_pick0, and
+    # the general kernels alone (GM_BAND_FAST=0 with GM_PICK0=0: gm_s_band + gm_s_pick, which the oracle
+    # pins at many bands, test_scaled_every_band_width_matches_oracle). Both are compared with the
+    # production path every tick, the gossip draws included.
+    kw = dict(rd_seed=7, init_mode=init_mode, init_t0=8 if init_mode else 0, init_seed=11, band=1024)
+    if loss == 2:  # as above: one keyed-loss tick between fast ticks, after a cold start's hand-backs
+        kw.update(drop_pct=20, drop_from=15, drop_to=16, drop_seed=5)
+    gen, fast = _pair(monkeypatch, n, **kw)
+    monkeypatch.setenv("GM_BAND_FAST", "0")
+    monkeypatch.setenv("GM_PICK0", "0")
+    plain = Simulator(n, GM_MODE_SCALED, **kw)
+    monkeypatch.delenv("GM_BAND_FAST")
+    monkeypatch.delenv("GM_PICK0")
+    sims = {"production path": fast, "general band kernel": gen, "general band and pick kernels": plain}
+    for s in sims.values():
+        s.msgcount_record(64)
+    crash = crash_set(n, (n * crash_pct + 99) // 100, 42)
+    for _ in range(56):
+        t = fast.time
+        for s in sims.values():
+            s.tick()
+            if t == 10:
+                s.set_failed(crash)
+        want = None
+        for name, s in sims.items():
+            got = {"events": [s.drain_events_np()], "tick stats": s.tick_stats(), "targets": s.read_targets(),
+                   "msgcount": s.msgcount(t)}
+            if t % 4 == 0 or 24 <= t <= 40:
+                got["tables"] = s.read_table(0, n)
+            if want is None:
+                want = got
+                continue
+            assert got["tick stats"] == want["tick stats"], f"tick stats differ at tick {t}: {name}"
+            for k in ("events", "targets", "msgcount", "tables"):
+                assert k not in want or _same_arrays(got[k], want[k]), f"{k} differ at tick {t}: {name}"
     assert fast.tick_stats()["err"] == 0
 
 
