@@ -47,6 +47,7 @@ hipError_t gm_launch_partial_mtgen(const PState &s, int t, uint32_t *mtraw, hipS
 hipError_t gm_launch_partial_reset(const PState &s, hipStream_t st);
 hipError_t gm_launch_partial_chunk(const PState &s, int t, const uint32_t *mtraw, int c, hipStream_t st);
 hipError_t gm_launch_msgcount(const SState &s, int t, bool dropped, int phase, hipStream_t st);
+hipError_t gm_launch_detect(const SState &s, gm_detect_rec *rec, uint64_t *timeline, int t, hipStream_t st);
 size_t gm_partial_lds_bytes();
 
 #define GM_T_LIMIT 32766  // packed 16-bit hb/ts stay exact: hb <= 2t+1 < 0xFFFF
@@ -94,6 +95,14 @@ struct gm_ctx {
   std::vector<void *> allocs;
   std::vector<int32_t> failed_h;
   std::vector<int32_t> fail_t;  // last tick a failed node ran (join ramp: its inGroup is frozen there)
+  // detection recorder (gm_detect_record; det_tmax 0 = off): per-subject records and the per-tick
+  // timeline [det_tmax][3]. SCALED keeps them on the device (gm_s_detect adds each tick's records),
+  // FAITHFUL on the host (f_collect)
+  int det_tmax = 0;
+  gm_detect_rec *det_rec = nullptr;  // device [s.w]
+  uint64_t *det_tl = nullptr;        // device [det_tmax][3]
+  std::vector<gm_detect_rec> det_h;  // FAITHFUL [n]
+  std::vector<uint64_t> det_tl_h;    // FAITHFUL [det_tmax][3]
   // FAITHFUL
   FState f{};
   size_t f_smem = 0;
@@ -795,6 +804,27 @@ static bool ev_order(const FEvent &a, const FEvent &b) {
 // the start / join / time-mark lines.
 static int64_t f_tick_event_bound(const gm_ctx *c) { return (int64_t)c->n * (2 * c->n + 4); }
 
+// FAITHFUL detection recorder: N <= 1000, so the records are aggregated here on the host, where
+// the tick's log lines are gathered. failed_h is the flag every collected tick ran with:
+// gm_set_failed and nodeStart's reset (tick_faithful) collect the enqueued ticks before they change it.
+static void detect_host(gm_ctx *c, int t, int kind, int subject) {
+  if (t >= c->det_tmax || subject < 1 || subject > c->n) return;  // det_tmax 0: off
+  gm_detect_rec &d = c->det_h[subject - 1];
+  uint64_t *row = c->det_tl_h.data() + 3 * (size_t)t;
+  if (kind == GM_EV_JOINED) {
+    d.joins++;
+    row[0]++;
+  } else if (kind == GM_EV_REMOVED) {
+    const bool live = !c->failed_h[subject - 1];
+    if (d.removals++ == 0) d.first_removed = t;
+    d.last_removed = t;
+    d.removed_tick_sum += (uint64_t)t;
+    d.false_removals += live;
+    row[1]++;
+    row[2] += live;
+  }
+}
+
 // Collect the mailbox of every tick enqueued since the last collection: one copy of the
 // count, the error flags and the first GM_F_MAILBOX records (more: a second copy), one
 // wait; the records are staged to `pending` in the reference's order, the count reset in
@@ -823,6 +853,7 @@ static int f_collect(gm_ctx *c) {
     for (const FEvent &e : ev) {
       c->pending.push_back(gm_event{e.t, e.logger, e.kind, e.subject});
       if (e.kind > 0 && e.kind < 6) c->ev_tot[e.kind]++;
+      detect_host(c, e.t, e.kind, e.subject);
     }
   }
   if (e) {
@@ -849,6 +880,7 @@ static int tick_faithful(gm_ctx *c) {
   // nodeStart of this tick's starters resets bFailed on the device (MP1Node.cpp:108-116); mirror it
   for (int i = 0; i < c->n; i++)
     if ((int)(0.25 * i) == c->t && c->failed_h[i]) {
+      if (c->det_tmax) TRY(f_collect(c));  // the recorder reads failed_h as the enqueued ticks saw it
       c->failed_h[i] = 0;
       c->fail_t[i] = 0x7FFFFFFF;
       c->nfailed--;
@@ -912,6 +944,15 @@ static int ramp_starters(gm_ctx *c) {
   return GM_OK;
 }
 
+// SCALED detection recorder: fold tick t's records into the per-subject records and the timeline
+// (gm_s_detect), on the stream that ran the tick's band kernels -- after them, and before the next
+// tick's prologue zeroes the record counters. Nothing is launched while recording is off.
+static int detect_tick(gm_ctx *c, int t, hipStream_t st) {
+  if (t >= c->det_tmax) return GM_OK;  // det_tmax 0: off
+  HIPCHECK(gm_launch_detect(c->s, c->det_rec, c->det_tl, t, st));
+  return GM_OK;
+}
+
 static int tick_scaled(gm_ctx *c) {
   if (c->t > GM_T_LIMIT) return GM_ERANGE;
   if (c->s.sharded) return tick_sharded(c);
@@ -921,6 +962,7 @@ static int tick_scaled(gm_ctx *c) {
   hipEvent_t k0 = nullptr, k1 = nullptr;
   if (c->timing) TRY(timing_slot(c, &k0, &k1));
   HIPCHECK(gm_launch_tick(c->s, c->t, drop ? c->cfg.drop_pct : -1, c->stream, k0, k1, true));
+  TRY(detect_tick(c, c->t, c->stream));
   if (c->s.mc_sent && c->t < c->s.mc_tmax) {
     HIPCHECK(gm_launch_msgcount(c->s, c->t, drop, 0, c->stream));
     HIPCHECK(gm_launch_msgcount(c->s, c->t, drop, 1, c->stream));
@@ -1308,6 +1350,55 @@ extern "C" int gm_event_totals(gm_ctx *c, uint64_t totals[6]) {
   }
   totals[0] = 0;
   for (int k = 1; k < 6; k++) totals[0] += totals[k];
+  return GM_OK;
+}
+
+// FAITHFUL / SCALED: detection records and timeline from the next tick on, for ticks < tmax
+extern "C" int gm_detect_record(gm_ctx *c, int32_t tmax) {
+  if (!c || tmax <= 0 || tmax > GM_T_LIMIT + 1) return GM_EINVAL;
+  if (c->cfg.mode == GM_MODE_PARTIAL) return GM_EUNSUPPORTED;
+  if (c->det_tmax) return GM_ESTATE;
+  TRY(f_settle(c));  // FAITHFUL: the ticks enqueued so far are collected unrecorded
+  const size_t rows = c->cfg.mode == GM_MODE_SCALED ? (size_t)c->s.w : (size_t)c->n;
+  std::vector<gm_detect_rec> init(rows, gm_detect_rec{-1, -1, -1, 0u, 0u, 0u, 0ull});
+  if (c->cfg.mode == GM_MODE_SCALED) {
+    TRY(dalloc(c, &c->det_rec, rows));
+    TRY(dalloc(c, &c->det_tl, 3 * (size_t)tmax));
+    HIPCHECK(ctx_memset(c, c->det_tl, 0, sizeof(uint64_t) * 3 * (size_t)tmax));
+    HIPCHECK(ctx_memcpy(c, c->det_rec, init.data(), sizeof(gm_detect_rec) * rows, hipMemcpyHostToDevice));
+  } else {
+    c->det_h.swap(init);
+    c->det_tl_h.assign(3 * (size_t)tmax, 0);
+  }
+  c->det_tmax = tmax;
+  return GM_OK;
+}
+
+extern "C" int gm_detect(gm_ctx *c, gm_detect_rec *out) {
+  if (!c || !out) return GM_EINVAL;
+  if (!c->det_tmax) return GM_ESTATE;
+  TRY(f_settle(c));
+  size_t rows = (size_t)c->n, c0 = 0;
+  if (c->cfg.mode == GM_MODE_SCALED) {
+    rows = (size_t)c->s.w;
+    c0 = (size_t)c->s.c0;
+    HIPCHECK(ctx_memcpy(c, out, c->det_rec, sizeof(gm_detect_rec) * rows, hipMemcpyDeviceToHost));
+  } else {
+    memcpy(out, c->det_h.data(), sizeof(gm_detect_rec) * rows);
+  }
+  for (size_t i = 0; i < rows; i++) out[i].fail_tick = c->failed_h[c0 + i] ? c->fail_t[c0 + i] : -1;
+  return GM_OK;
+}
+
+extern "C" int gm_detect_timeline(gm_ctx *c, int32_t t, uint64_t *out) {
+  if (!c || !out) return GM_EINVAL;
+  if (!c->det_tmax) return GM_ESTATE;
+  if (t <= 0 || t > c->det_tmax) return GM_EINVAL;
+  TRY(f_settle(c));
+  if (c->cfg.mode == GM_MODE_SCALED)
+    HIPCHECK(ctx_memcpy(c, out, c->det_tl, sizeof(uint64_t) * 3 * (size_t)t, hipMemcpyDeviceToHost));
+  else
+    memcpy(out, c->det_tl_h.data(), sizeof(uint64_t) * 3 * (size_t)t);
   return GM_OK;
 }
 
@@ -1858,6 +1949,7 @@ extern "C" int gm_shard_merge(gm_ctx *c) {
   hipEvent_t k0 = nullptr, k1 = nullptr;
   if (c->timing) TRY(timing_slot(c, &k0, &k1));
   HIPCHECK(gm_launch_tick(c->s, c->t, drop ? c->cfg.drop_pct : -1, c->stream, k0, k1, false));
+  TRY(detect_tick(c, c->t, c->stream));
   HIPCHECK(gm_launch_xrows(c->s, 0, c->n, c->stream));  // this shard's row totals for the all-gather
   // msgcount: this shard's fresh counts (its columns), SUM-allreduced before the draws
   if (mc_on(c, c->t)) HIPCHECK(gm_launch_msgcount(c->s, c->t, drop, 0, c->stream));
@@ -1981,6 +2073,7 @@ extern "C" int gm_shard_loopback_tick(gm_ctx **ctxs, int32_t G) {
       const int r0 = ch << s.xlog;
       HIPCHECK(gm_launch_band_rows(s, t, drop ? c->cfg.drop_pct : -1, r0, r0 + xchunk_rows(s, ch), ls));
     }
+    TRY(detect_tick(c, t, ls));
   }
   auto max_reduce = [&](auto buf_of, size_t off, size_t cnt) -> int {  // MAX over the shards, into every shard
     if (!cnt) return GM_OK;
@@ -2232,6 +2325,7 @@ static int tick_sharded(gm_ctx *c) {
       HIPCHECK(hipEventRecord(c->p_chev[ch], c->stream));
     }
     if (k1) HIPCHECK(hipEventRecord(k1, c->stream));
+    TRY(detect_tick(c, t, c->stream));  // on the compute stream, beside the comm stream's draws
     hipStream_t cs = c->p_comm;
     for (int ch = 0; ch < s.xk; ch++) {
       const int r0 = ch << s.xlog, r1 = r0 + xchunk_rows(s, ch);

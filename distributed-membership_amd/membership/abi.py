@@ -33,7 +33,19 @@ class GmEvent(ctypes.Structure):
                 ("subject", ctypes.c_int32)]
 
 
-EXPORTS = ["gm_parse_conf", "gm_create", "gm_destroy", "gm_tick", "gm_sync", "gm_time", "gm_rand", "gm_set_failed",
+class GmDetectRec(ctypes.Structure):
+    _fields_ = [("fail_tick", ctypes.c_int32), ("first_removed", ctypes.c_int32), ("last_removed", ctypes.c_int32),
+                ("removals", ctypes.c_uint32), ("false_removals", ctypes.c_uint32), ("joins", ctypes.c_uint32),
+                ("removed_tick_sum", ctypes.c_uint64)]
+
+
+# gm_detect_rec as a NumPy structured dtype (32 bytes, the field names of include/gm_abi.h)
+DETECT_DTYPE = np.dtype([("fail_tick", "<i4"), ("first_removed", "<i4"), ("last_removed", "<i4"),
+                         ("removals", "<u4"), ("false_removals", "<u4"), ("joins", "<u4"),
+                         ("removed_tick_sum", "<u8")])
+assert DETECT_DTYPE.itemsize == ctypes.sizeof(GmDetectRec) == 32
+
+EXPORTS = ["gm_detect_record", "gm_detect", "gm_detect_timeline", "gm_parse_conf", "gm_create", "gm_destroy", "gm_tick", "gm_sync", "gm_time", "gm_rand", "gm_set_failed",
            "gm_set_dropmsg", "gm_drain_events", "gm_event_counts", "gm_msgcount", "gm_read_row", "gm_read_table", "gm_read_nodes",
            "gm_dump_tables", "gm_tick_stats", "gm_set_timing", "gm_last_kernel_ms", "gm_crash_set", "gm_strerror",
            "gm_comm_unique_id", "gm_comm_init", "gm_shard_layout", "gm_shard_merge", "gm_shard_draw",
@@ -72,6 +84,8 @@ def load_library():
         "gm_keep_events": [ctypes.c_void_p, i32], "gm_shard_stub": [ctypes.c_void_p, i32], "gm_read_views": [ctypes.c_void_p, i32, i32, P(u64)],
         "gm_msgcount": [ctypes.c_void_p, i32, P(i32), P(i32)],
         "gm_msgcount_record": [ctypes.c_void_p, i32],
+        "gm_detect_record": [ctypes.c_void_p, i32], "gm_detect": [ctypes.c_void_p, P(GmDetectRec)],
+        "gm_detect_timeline": [ctypes.c_void_p, i32, P(u64)],
         "gm_read_row": [ctypes.c_void_p, i32, i32, i32, P(i32), P(i32)],
         "gm_read_table": [ctypes.c_void_p, i32, i32, P(i32), P(i32)],
         "gm_read_nodes": [ctypes.c_void_p, P(i32)], "gm_read_targets": [ctypes.c_void_p, P(i32), P(i32)],
@@ -251,6 +265,25 @@ class Simulator:
         recv = np.zeros((rows, t), dtype=np.int32)
         self._call("gm_msgcount", self.h, t, _ptr(sent), _ptr(recv))
         return sent, recv
+
+    def detect_record(self, tmax):
+        """FAITHFUL / SCALED: record detection statistics from the next tick on, for ticks < tmax"""
+        self._call("gm_detect_record", self.h, tmax)
+
+    def detect(self):
+        """One gm_detect_rec per subject this context owns (a SCALED column shard: its columns), as a
+        structured array with the fields fail_tick, first_removed, last_removed, removals,
+        false_removals, joins, removed_tick_sum."""
+        rows = self.shard_layout()[1] if self.mode == GM_MODE_SCALED else self.n
+        out = np.zeros(rows, dtype=DETECT_DTYPE)
+        self._call("gm_detect", self.h, out.ctypes.data_as(ctypes.POINTER(GmDetectRec)))
+        return out
+
+    def detect_timeline(self, t):
+        """uint64 [t, 3]: joins, removals, false removals recorded in each tick < t"""
+        out = np.zeros((t, 3), dtype=np.uint64)
+        self._call("gm_detect_timeline", self.h, t, _ptr(out, ctypes.c_uint64))
+        return out
 
     def read_row(self, r, c0=0, length=None):
         length = self.n if length is None else length

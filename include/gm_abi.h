@@ -24,6 +24,8 @@
  *   gm_set_dropmsg  par->dropmsg = 0/1 (Application.cpp:178,199)
  *   gm_drain_events Log::LOG / logNodeAdd / logNodeRemove call sites inside the tick
  *                   (Log.cpp:44-131; MP1Node.cpp:135,153,295,437; Application.cpp:158)
+ *   gm_detect       Log::logNodeAdd / logNodeRemove (Log.cpp:116-131) as the grader reads their
+ *                   lines: who was removed, by how many observers, when, and who by mistake
  *   gm_msgcount     EmulNet::sent_msgs / recv_msgs as dumped by ENcleanup (EmulNet.cpp:184-220)
  *   gm_dump_tables  Member::memberList of every node (Member.h:89-122), for parity tests
  *   gm_destroy      Application::~Application / ENcleanup storage release
@@ -162,7 +164,8 @@ int gm_drain_events(gm_ctx *ctx, gm_event *out, size_t cap, size_t *n);
  * gm_drain_events then returns the last tick's records only.
  * Limits: with on = 1 the host stages at most 2^27 records between drains (GM_ERANGE
  * beyond: a TREMOVE tick of S-B's 1 % crash removes ~687 M entries, of S-A's ~22 M);
- * clusters that large run with on = 0 and read the device totals (gm_event_totals). The
+ * clusters that large run with on = 0 and read the device totals (gm_event_totals) or the
+ * per-subject detection records (gm_detect_record). The
  * device keeps E = band/32 records per (row, band) plus a spill ring sized from free HBM
  * (>= 2^24 records; GM_ERR_EVENTS -> GM_ERANGE past it). */
 int gm_keep_events(gm_ctx *ctx, int32_t on);
@@ -189,6 +192,34 @@ int gm_msgcount(gm_ctx *ctx, int32_t t, int32_t *sent, int32_t *recv);
  * SUM-allreduce them (N x 4 B per tick, only while recording), so every rank returns the
  * whole cluster's counts, equal to the single-context ones. */
 int gm_msgcount_record(gm_ctx *ctx, int32_t tmax);
+
+/* ---- failure-detection statistics (FAITHFUL, SCALED). The reference's grader reads completeness
+ * and accuracy out of dbg.log's "joined" / "removed" lines (Log::logNodeAdd / logNodeRemove,
+ * Log.cpp:116-131, called from MP1Node.cpp:295,437). The recorder keeps what the grader derives
+ * from them, per subject node and per tick, without draining: SCALED reduces each tick's records
+ * on the device before the next tick overwrites them (independent of gm_keep_events), FAITHFUL
+ * aggregates where it collects its records. */
+typedef struct gm_detect_rec {      /* 32 bytes, one per subject node */
+  int32_t  fail_tick;        /* the tick after which gm_set_failed marked the node; -1 = never failed */
+  int32_t  first_removed;    /* tick of the first REMOVED record naming this subject; -1 = none */
+  int32_t  last_removed;     /* tick of the last one; -1 = none */
+  uint32_t removals;         /* REMOVED records naming this subject */
+  uint32_t false_removals;   /* those logged in a tick during which the subject's bFailed was 0 */
+  uint32_t joins;            /* JOINED records naming this subject */
+  uint64_t removed_tick_sum; /* sum of the ticks of its removals
+                                (mean latency = sum / removals - fail_tick) */
+} gm_detect_rec;
+/* Start recording from the next tick, for ticks < tmax (0 < tmax <= 32767, else GM_EINVAL); a tick
+ * >= tmax is not recorded at all. May be called between any two ticks; a second call returns
+ * GM_ESTATE. PARTIAL: GM_EUNSUPPORTED (views churn ~V joins per node and tick, and a removal there
+ * is an eviction). While recording is off no kernel is added to a tick. */
+int gm_detect_record(gm_ctx *ctx, int32_t tmax);
+/* One record per subject this context owns: out[n], or out[w] for a SCALED column shard over the
+ * columns [c0, c0 + w) of gm_shard_layout. GM_ESTATE before gm_detect_record. */
+int gm_detect(gm_ctx *ctx, gm_detect_rec *out);
+/* out[t][3] = joins, removals, false removals recorded in tick i, for i < t <= tmax (ticks before
+ * recording began: 0). A column shard reports its own columns. */
+int gm_detect_timeline(gm_ctx *ctx, int32_t t, uint64_t *out);
 
 /* Dense readback of observer row r: hb/ts per subject column (absent -> -1),
  * columns [c0, c0+len) of this context's shard (c0 relative to the shard start). */
