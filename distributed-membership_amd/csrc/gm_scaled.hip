@@ -1458,6 +1458,14 @@ __global__ __launch_bounds__(256) void gm_s_band_listed(SState s, int t, int u0,
 #define GM_FAST_WG 1  // waves per workgroup of gm_s_band_fast (1: a finished wave frees its LDS slice at once;
                       // 4: 3.29 ms per S-A tick, 1: 3.22, profiles/r06/ab_fwg/)
 #endif
+// XS: the row interleave of the grid's x. Workgroups are dealt to the XCDs round-robin in practice (no
+// promise of HIP's: only the speed rests on it), so with XS = 8 one XCD walks consecutive rows of a band
+// pair: the rows' shared metadata lines (16 rows per line of the crash flag and of the inbox count, 4
+// per line of records) are fetched into one L2, not eight, and the record stores fill their lines in
+// one L2. 1: rows in grid order.
+#ifndef GM_FAST_XS
+#define GM_FAST_XS 8
+#endif
 template <int B, bool CH, int BPW>
 #ifndef GM_FAST_MINW
 #define GM_FAST_MINW 7  // gm_s_band_fast's waves per SIMD (72 VGPRs at 7)
@@ -1468,8 +1476,12 @@ __global__ __launch_bounds__(64 * GM_FAST_WG) __attribute__((amdgpu_waves_per_eu
     u1 = s.n;
   }
   const int wv = GM_FAST_WG == 1 ? 0 : (int)(threadIdx.x >> 6);
-  const int ub = __builtin_amdgcn_readfirstlane(u0 + (int)blockIdx.x * GM_FAST_WG + wv);
-  if (ub >= u1) return;  // whole wave (one row per wave)
+  // wave w of the grid's x takes row u0 + (w % XS) * q + w / XS: the XS stripes of q consecutive rows
+  // interleave over the grid, so the workgroups XS apart walk one stripe row by row
+  const uint32_t w = (uint32_t)((int)blockIdx.x * GM_FAST_WG + wv);
+  const uint32_t q = (uint32_t)(u1 - u0 + GM_FAST_XS - 1) / GM_FAST_XS;
+  const int ub = __builtin_amdgcn_readfirstlane(u0 + (int)((w % GM_FAST_XS) * q + w / GM_FAST_XS));
+  if ((GM_FAST_WG > 1 && w / GM_FAST_XS >= q) || ub >= u1) return;  // whole wave (one row per wave)
   // per wave: escape cells by column, the park, the per-lane words of the escaped cells' outcomes
   constexpr int W = 2 * S_LDS_WAVE_WORDS + 192;
   __shared__ uint32_t lds_all[GM_FAST_WG * W];
@@ -2592,7 +2604,9 @@ static void launch_band_b(const SState &s, int t, int drop_pct, int r0, int r1, 
   if (drop_pct >= 0) {
     hipLaunchKernelGGL((gm_s_band<B, true>), dim3(nblk), dim3(256), 0, st, s, t, drop_pct, u0, u1);
   } else if (B == 1024 && !s.ramp && s.fb_list) {  // the fast path, then the units it handed back
-    const dim3 nblk2((u1 - u0 + GM_FAST_WG - 1) / GM_FAST_WG, (s.nb + GM_FAST_BPW - 1) / GM_FAST_BPW);
+    // GM_FAST_XS stripes of q rows each (the kernel's row order); waves past u1 exit
+    const int q = (u1 - u0 + GM_FAST_XS - 1) / GM_FAST_XS;
+    const dim3 nblk2((GM_FAST_XS * q + GM_FAST_WG - 1) / GM_FAST_WG, (s.nb + GM_FAST_BPW - 1) / GM_FAST_BPW);
     if (u0 == 0 && r1 == s.n)
       hipLaunchKernelGGL((gm_s_band_fast<B == 1024 ? B : 1024, false, GM_FAST_BPW>), nblk2, dim3(64 * GM_FAST_WG), 0,
                          st, s, t, u0, u1);
