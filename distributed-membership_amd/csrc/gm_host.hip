@@ -48,6 +48,14 @@ hipError_t gm_launch_partial_reset(const PState &s, hipStream_t st);
 hipError_t gm_launch_partial_chunk(const PState &s, int t, const uint32_t *mtraw, int c, hipStream_t st);
 hipError_t gm_launch_msgcount(const SState &s, int t, bool dropped, int phase, hipStream_t st);
 hipError_t gm_launch_detect(const SState &s, gm_detect_rec *rec, uint64_t *timeline, int t, hipStream_t st);
+hipError_t gm_launch_load_check(const SState &s, int t, int r0, int cnt, const int32_t *hb, const int32_t *ts,
+                                int32_t *base, int32_t *own, uint32_t *status, hipStream_t st);
+hipError_t gm_launch_load_encode(const SState &s, int t, int r0, int cnt, const int32_t *hb, const int32_t *ts,
+                                 const int32_t *base, hipStream_t st);
+hipError_t gm_launch_load_nodes(const SState &s, int t, const int32_t *heartbeat, const int32_t *failed,
+                                const int32_t *targets, const int32_t *counts, const int32_t *own, uint32_t *status,
+                                int write, hipStream_t st);
+hipError_t gm_launch_load_inbox(const SState &s, int t, uint32_t *status, hipStream_t st);
 size_t gm_partial_lds_bytes();
 
 #define GM_T_LIMIT 32766  // packed 16-bit hb/ts stay exact: hb <= 2t+1 < 0xFFFF
@@ -111,6 +119,21 @@ struct gm_ctx {
   std::vector<gm_event> pending;
   // SCALED
   SState s{};
+  // SCALED state loading (gm_load_begin .. gm_load_commit). One device block (ld_blob, freed by the
+  // commit): the staged (hb, ts) of up to ld_cap rows, their base ticks, every row's own entry
+  // as staged, the node arrays of the commit, the status word of a call's checks.
+  bool loading = false;              // between gm_load_begin and a successful gm_load_commit
+  bool load_void = false;            // a load call failed: only gm_load_begin starts over
+  int load_t = 0;                    // gm_load_begin's t
+  int ld_cap = 0;                    // staged rows per encode launch
+  void *ld_blob = nullptr;
+  size_t ld_bytes = 0;
+  int32_t *ld_hb = nullptr, *ld_ts = nullptr, *ld_base = nullptr, *ld_own = nullptr, *ld_nodes = nullptr;
+  uint32_t *ld_status = nullptr;
+  std::vector<uint8_t> ld_seen;      // rows given so far
+  int64_t ld_rows = 0;
+  double ld_ms[2] = {0, 0};          // gm_set_timing on: ms in gm_l_check / gm_l_encode since gm_load_begin
+  hipEvent_t ld_ev[3] = {nullptr, nullptr, nullptr};
   // PARTIAL
   PState p{};
   uint32_t *p_mtraw = nullptr;        // [2][nloc][16] S2 outputs by tick parity
@@ -760,6 +783,9 @@ extern "C" int gm_destroy(gm_ctx *c) {
   if (c->p_comm) (void)hipStreamSynchronize(c->p_comm);
   if (c->comm) (void)ncclCommDestroy(c->comm);
   for (void *p : c->allocs) (void)hipFree(p);
+  if (c->ld_blob) (void)hipFree(c->ld_blob);
+  for (hipEvent_t e : c->ld_ev)
+    if (e) (void)hipEventDestroy(e);
   if (c->draw_left_h) (void)hipHostFree(c->draw_left_h);
   if (c->draw_ev) (void)hipEventDestroy(c->draw_ev);
   if (c->f_mail) (void)hipHostFree(c->f_mail);
@@ -1052,6 +1078,7 @@ static int tick_partial(gm_ctx *c) {
 extern "C" int gm_tick(gm_ctx *c) {
   if (!c) return GM_EINVAL;
   if (c->latched != GM_OK) return c->latched;
+  if (c->loading) return GM_ESTATE;  // between gm_load_begin and gm_load_commit
   if (c->cfg.mode == GM_MODE_SCALED) TRY(draw_settle(c));
   TRY(before_tick_events(c));
   int rc = c->cfg.mode == GM_MODE_FAITHFUL ? tick_faithful(c) : c->cfg.mode == GM_MODE_SCALED ? tick_scaled(c)
@@ -1099,6 +1126,7 @@ extern "C" int gm_set_failed(gm_ctx *c, const int32_t *idx, int32_t n) {
   if (!c || n < 0 || (n > 0 && !idx)) return GM_EINVAL;
   for (int k = 0; k < n; k++)  // validate everything before any state changes
     if (idx[k] < 0 || idx[k] >= c->n) return GM_EINVAL;
+  if (c->loading) return GM_ESTATE;  // the commit sets the crash flags
   TRY(f_settle(c));
   for (int k = 0; k < n; k++) {
     c->nfailed += c->failed_h[idx[k]] == 0;
@@ -1764,6 +1792,175 @@ extern "C" int gm_read_targets(gm_ctx *c, int32_t *targets, int32_t *counts) {
   return check_err(c);
 }
 
+// ------------------------------------------------------------------ SCALED state loading
+// gm_load_begin / gm_load_rows / gm_load_commit (gm_load.hip has the kernels and what they check).
+#define GM_LOAD_STAGE_BYTES (256ull << 20)  // staged (hb, ts) of one encode launch; + 44 B per node: < 512 MiB
+
+static void load_free(gm_ctx *c) {
+  if (c->ld_blob) (void)hipFree(c->ld_blob);
+  c->ld_blob = nullptr;
+  c->ld_hb = c->ld_ts = c->ld_base = c->ld_own = c->ld_nodes = nullptr;
+  c->ld_status = nullptr;
+  c->ld_cap = 0;
+  std::vector<uint8_t>().swap(c->ld_seen);
+}
+
+// the status word of the load kernels enqueued so far; a failure voids the load (gm_load_begin starts over)
+static int load_status(gm_ctx *c, const char *what) {
+  uint32_t st = 0;
+  HIPCHECK(ctx_memcpy(c, &st, c->ld_status, sizeof st, hipMemcpyDeviceToHost));
+  if (!st) return GM_OK;
+  HIPCHECK(ctx_memset(c, c->ld_status, 0, sizeof st));
+  c->load_void = true;
+  snprintf(g_errbuf, sizeof g_errbuf, "%s: state rejected (check flags 0x%x)", what, st);
+  return (st & GM_LD_EINVAL) ? GM_EINVAL : GM_ERANGE;
+}
+
+extern "C" int gm_load_begin(gm_ctx *c, int32_t t) {
+  if (!c) return GM_EINVAL;
+  if (c->cfg.mode != GM_MODE_SCALED || c->s.ramp || c->s.mc_sent) return GM_EUNSUPPORTED;
+  if (t < 1 || t > GM_T_LIMIT) return GM_EINVAL;
+  if (c->latched != GM_OK) return c->latched;
+  SState &s = c->s;
+  if (!c->loading) {  // settle the run so far; its device error, if any, is the caller's to see
+    TRY(draw_settle(c));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    TRY(check_err(c));
+  } else {
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    HIPCHECK(ctx_memset(c, s.err, 0, sizeof(uint32_t)));  // a voided load's pool overflow
+  }
+  const size_t n = (size_t)c->n, w = (size_t)s.w;
+  size_t cap = std::min<size_t>(n, std::max<size_t>(1, GM_LOAD_STAGE_BYTES / (2 * sizeof(int32_t) * w)));
+  if (getenv("GM_LOAD_STAGE_ROWS"))  // diagnostics (tests): smaller encode launches
+    cap = std::max<size_t>(1, std::min<size_t>(cap, (size_t)atol(getenv("GM_LOAD_STAGE_ROWS"))));
+  if (!c->ld_blob || (size_t)c->ld_cap != cap) {
+    load_free(c);
+    // int32 words: hb, ts [cap][w]; base [cap]; own [n][2]; heartbeat, failed, counts [n], targets [n][5]; status
+    const size_t words = 2 * cap * w + cap + 2 * n + (3 + GM_FANOUT) * n + 4;
+    if (hipMalloc(&c->ld_blob, words * sizeof(int32_t)) != hipSuccess) {
+      c->ld_blob = nullptr;
+      snprintf(g_errbuf, sizeof g_errbuf, "hipMalloc(%zu) failed (load staging)", words * sizeof(int32_t));
+      return GM_ENOMEM;
+    }
+    c->ld_bytes = words * sizeof(int32_t);
+    c->ld_cap = (int)cap;
+    c->ld_hb = (int32_t *)c->ld_blob;
+    c->ld_ts = c->ld_hb + cap * w;
+    c->ld_base = c->ld_ts + cap * w;
+    c->ld_own = c->ld_base + cap;
+    c->ld_nodes = c->ld_own + 2 * n;
+    c->ld_status = (uint32_t *)(c->ld_nodes + (3 + GM_FANOUT) * n);
+  }
+  HIPCHECK(ctx_memset(c, c->ld_status, 0, sizeof(uint32_t)));
+  HIPCHECK(ctx_memset(c, c->ld_own, 0xFF, sizeof(int32_t) * 2 * n));
+  // the escape lists and payload slots of parity (t - 1) & 1 are allocated by the encode; the other
+  // parity's counters are the next tick's, zeroed "a tick ahead" (band_reset_pools)
+  HIPCHECK(ctx_memset(c, s.tesc_cnt, 0, 2 * (size_t)s.esc_stripes * sizeof(unsigned long long)));
+  HIPCHECK(ctx_memset(c, s.pesc_cnt, 0, 2 * (size_t)s.esc_stripes * sizeof(unsigned long long)));
+  if (s.fb_cnt) HIPCHECK(ctx_memset(c, s.fb_cnt, 0, 2 * sizeof(uint32_t)));
+  c->loading = true;
+  c->load_void = false;
+  c->load_t = t;
+  c->ld_seen.assign(n, 0);
+  c->ld_rows = 0;
+  c->ld_ms[0] = c->ld_ms[1] = 0;
+  return GM_OK;
+}
+
+extern "C" int gm_load_rows(gm_ctx *c, int32_t r0, int32_t count, const int32_t *hb, const int32_t *ts) {
+  if (!c || r0 < 0 || count < 0 || r0 + (int64_t)count > c->n || (count > 0 && (!hb || !ts))) return GM_EINVAL;
+  if (!c->loading || c->load_void) return GM_ESTATE;
+  for (int i = 0; i < count; i++)
+    if (c->ld_seen[r0 + i]) return GM_ESTATE;  // each row exactly once
+  const SState &s = c->s;
+  const size_t w = (size_t)s.w;
+  if (c->timing)
+    for (hipEvent_t &e : c->ld_ev)
+      if (!e) HIPCHECK(hipEventCreate(&e));
+  for (int off = 0; off < count; off += c->ld_cap) {
+    const int m = std::min(c->ld_cap, count - off), rb = r0 + off;
+    HIPCHECK(ctx_memcpy(c, c->ld_hb, hb + (size_t)off * w, sizeof(int32_t) * m * w, hipMemcpyHostToDevice));
+    HIPCHECK(ctx_memcpy(c, c->ld_ts, ts + (size_t)off * w, sizeof(int32_t) * m * w, hipMemcpyHostToDevice));
+    if (c->timing) HIPCHECK(hipEventRecord(c->ld_ev[0], c->stream));
+    HIPCHECK(gm_launch_load_check(s, c->load_t, rb, m, c->ld_hb, c->ld_ts, c->ld_base, c->ld_own, c->ld_status, c->stream));
+    if (c->timing) HIPCHECK(hipEventRecord(c->ld_ev[1], c->stream));
+    TRY(load_status(c, "gm_load_rows"));  // nothing of the block is written before its checks pass
+    if (c->timing) {  // (load_status waited for the stream)
+      float a = 0;
+      HIPCHECK(hipEventElapsedTime(&a, c->ld_ev[0], c->ld_ev[1]));
+      c->ld_ms[0] += a;
+      HIPCHECK(hipEventRecord(c->ld_ev[0], c->stream));
+    }
+    HIPCHECK(gm_launch_load_encode(s, c->load_t, rb, m, c->ld_hb, c->ld_ts, c->ld_base, c->stream));
+    if (c->timing) {
+      float b = 0;
+      HIPCHECK(hipEventRecord(c->ld_ev[2], c->stream));
+      HIPCHECK(hipStreamSynchronize(c->stream));
+      HIPCHECK(hipEventElapsedTime(&b, c->ld_ev[0], c->ld_ev[2]));
+      c->ld_ms[1] += b;
+    }
+    for (int i = 0; i < m; i++) c->ld_seen[rb + i] = 1;
+    c->ld_rows += m;
+  }
+  return GM_OK;
+}
+
+extern "C" int gm_load_commit(gm_ctx *c, const int32_t *heartbeat, const int32_t *failed, const int32_t *targets,
+                              const int32_t *counts) {
+  if (!c || !heartbeat || !failed || !targets || !counts) return GM_EINVAL;
+  if (!c->loading || c->load_void || c->ld_rows != c->n) return GM_ESTATE;  // rows missing
+  SState &s = c->s;
+  const size_t n = (size_t)c->n;
+  const int t = c->load_t;
+  int32_t *d_hb = c->ld_nodes, *d_f = d_hb + n, *d_cnt = d_f + n, *d_tg = d_cnt + n;
+  HIPCHECK(ctx_memcpy(c, d_hb, heartbeat, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+  HIPCHECK(ctx_memcpy(c, d_f, failed, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+  HIPCHECK(ctx_memcpy(c, d_cnt, counts, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+  HIPCHECK(ctx_memcpy(c, d_tg, targets, sizeof(int32_t) * n * GM_FANOUT, hipMemcpyHostToDevice));
+  uint32_t e = 0;  // the encode's own flag: an escape pool too small for this state
+  HIPCHECK(ctx_memcpy(c, &e, s.err, sizeof e, hipMemcpyDeviceToHost));
+  if (e) {
+    HIPCHECK(ctx_memset(c, s.err, 0, sizeof e));
+    c->load_void = true;
+    snprintf(g_errbuf, sizeof g_errbuf, "gm_load_commit: the state overflows the escape pools (flags 0x%x)", e);
+    return GM_ERANGE;
+  }
+  HIPCHECK(gm_launch_load_nodes(s, t, d_hb, d_f, d_tg, d_cnt, c->ld_own, c->ld_status, 0, c->stream));
+  TRY(load_status(c, "gm_load_commit"));
+  for (int p = 0; p < 2; p++) HIPCHECK(ctx_memset(c, s.inbox_cnt[p], 0, sizeof(int32_t) * n));
+  HIPCHECK(gm_launch_load_nodes(s, t, d_hb, d_f, d_tg, d_cnt, c->ld_own, c->ld_status, 1, c->stream));
+  HIPCHECK(gm_launch_load_inbox(s, t, c->ld_status, c->stream));
+  TRY(load_status(c, "gm_load_commit"));  // an inbox past its capacity: GM_ERANGE
+  // as a tick would have left it: no records of a last tick (the totals and the recorder carry on)
+  HIPCHECK(ctx_memset(c, s.ev_spill_cnt, 0, (1 + S_EV_STRIPES) * sizeof(uint32_t)));
+  c->pending.clear();
+  c->undrained = false;
+  c->nfailed = 0;
+  for (size_t i = 0; i < n; i++) {
+    // a node that was crashed before the load and still is keeps the tick it failed at (gm_detect's
+    // fail_tick); one the load crashes counts as failed at the end of tick t - 1
+    if (!failed[i]) c->fail_t[i] = 0x7FFFFFFF;
+    else if (!c->failed_h[i]) c->fail_t[i] = t - 1;
+    c->failed_h[i] = failed[i];
+    c->nfailed += failed[i] != 0;
+  }
+  c->t = t;
+  c->loading = false;
+  load_free(c);
+  return GM_OK;
+}
+
+extern "C" int gm_load_stats(gm_ctx *c, double stats[4]) {
+  if (!c || !stats) return GM_EINVAL;
+  if (c->cfg.mode != GM_MODE_SCALED) return GM_EUNSUPPORTED;
+  stats[0] = (double)c->ld_rows;
+  stats[1] = (double)c->ld_bytes;
+  stats[2] = c->ld_ms[0];
+  stats[3] = c->ld_ms[1];
+  return GM_OK;
+}
+
 extern "C" int gm_tick_stats(gm_ctx *c, int64_t stats[4]) {
   if (!c || !stats) return GM_EINVAL;
   if (c->cfg.mode == GM_MODE_FAITHFUL) return GM_EUNSUPPORTED;
@@ -1935,6 +2132,7 @@ static bool mc_on(const gm_ctx *c, int t) { return c->s.mc_sent && t < c->s.mc_t
 static int shard_ready(gm_ctx *c) {
   if (!c || c->cfg.mode != GM_MODE_SCALED || !c->s.sharded) return GM_EINVAL;
   if (c->latched != GM_OK) return c->latched;
+  if (c->loading) return GM_ESTATE;  // between gm_load_begin and gm_load_commit
   if (c->t > GM_T_LIMIT) return GM_ERANGE;
   return GM_OK;
 }

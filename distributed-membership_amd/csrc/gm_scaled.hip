@@ -34,10 +34,6 @@
 
 #include <algorithm>
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
-typedef uint8_t u8x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 // ------------------------------------------------------------------ gm_s_mtgen
 // Also zeroes the tick's counters (no fill launch of their own each tick): the event spill ring's
@@ -150,215 +146,6 @@ __device__ __forceinline__ RowMeta<B> row_meta(const SState &s, int r, int par, 
   return m;
 }
 
-// Buffer resource over [p, p + bytes) built from wave-uniform values (SGPRs): loads
-// beyond `bytes` return 0 without touching memory, stores beyond it are dropped.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t gm_rsrc(const void *p, uint32_t bytes) {
-  const uint64_t a = (uint64_t)p;
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), (short)0,
-                                           (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-#define GM_AUX_NT 2  // non-temporal (streamed once)
-#define GM_OOB 0x80000000u
-
-// Packed 16-bit lanes of a 32-bit register: two cells per VGPR, v_pk_* arithmetic.
-typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u16x2 pk(uint32_t v) { return __builtin_bit_cast(u16x2, v); }
-__device__ __forceinline__ uint32_t unpk(u16x2 v) { return __builtin_bit_cast(uint32_t, v); }
-// payload bytes 0,1 / 2,3 of a dword, zero-extended into the two halves
-// a += b per u16 half, opaque to the compiler: plain vector adds of the sweep's
-// per-pair counts get re-associated into a tree that keeps every pair's term live
-// (9 VGPR spills at occupancy 8); an in-order chain consumes each term at once
-__device__ __forceinline__ u16x2 padd(u16x2 a, u16x2 b) {
-  uint32_t r;
-  asm("v_pk_add_u16 %0, %1, %2" : "=v"(r) : "v"(unpk(a)), "v"(unpk(b)));
-  return pk(r);
-}
-// min(x, 1) per u16 half as ONE v_pk_min_u16: written as plain vector min the compiler
-// lowers it to a compare + select per half (5 instructions instead of 1)
-__device__ __forceinline__ u16x2 pmin1(u16x2 a) {
-  uint32_t r;
-  asm("v_pk_min_u16 %0, %1, 1 op_sel_hi:[1,0]" : "=v"(r) : "v"(unpk(a)));
-  return pk(r);
-}
-
-// stored cell bytes 0,1 (hi = 0) or 2,3 (hi = 1) of a dword, zero-extended into the two u16 halves
-__device__ __forceinline__ uint32_t byte_pair(uint32_t w, int hi) {
-  return __builtin_amdgcn_perm(0u, w, hi ? 0x0c030c02u : 0x0c010c00u);
-}
-// s_widen of two stored bytes (nz = min(x, 1)); an escape byte gives garbage, replaced by its wide cell
-// (h4 << 4 | a -> 7168 + (h4 << 6) + a = x + 3 (x & 0xF0) + 7168: two multiply-adds)
-__device__ __forceinline__ u16x2 widen2(u16x2 x, u16x2 nz) {
-  return nz * (u16x2)(7168) + ((x & (u16x2)(0xF0)) * (u16x2)(3) + x);
-}
-
-// wave-wide inclusive scan on DPP: row_shr 1/2/4/8 within each 16-lane row, row_bcast15 /
-// row_bcast31 carry the row totals upward (lanes a DPP source does not reach add 0)
-__device__ __forceinline__ int dpp_scan(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);  // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);  // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);  // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);  // row_shr:8
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
-  return v;
-}
-
-// Stored bytes of two swept cells (pres = min(v2, 1)): tt = v2 - (S_CELL(230, 0) - 1) (wraps below
-// h = 230) = (h - 230) << 5 | (age + 1); representable iff nothing above the h field (h <= 254, no
-// wrap), h even (bit 5) and age <= 14 (bit 4 of age + 1) -> h4 << 4 | age (h4 = (h - 224) / 2 =
-// the tt field + 3), else S_B_ESC (bad = 1); absent 0. gm_scaled.h: a stored byte is always one
-// re-base away from another byte, which the fast path of gm_s_band relies on.
-__device__ __forceinline__ u16x2 narrow2(u16x2 v2, u16x2 pres, u16x2 &bad) {
-  const u16x2 tt = v2 - (u16x2)(S_CELL(S_H4_MIN_H, 0) - 1);
-  bad = pmin1(tt & (u16x2)(0xFC30)) & pres;
-  const uint32_t tu = unpk(tt);
-  const u16x2 enc = pk((tu & 0x000F000Fu) | ((tu >> 2) & 0x00F000F0u)) + (u16x2)(0x2F);
-  return enc * (pres - bad) + bad;
-}
-
-// The lane's escaped cells as a mask: bit 8j + i set where byte j of stored dword i (cell 4i + j)
-// is the escape code S_B_ESC (the narrowing writes no other code below 16). x = w ^ 0x01010101 has
-// a zero byte exactly there (carry-free SWAR zero-byte test); the four dwords' byte flags are
-// merged by shifts alone (no quarter-rate 32-bit multiply to gather them). esc_cell maps a bit
-// back to its cell; the list's entries carry their columns, so their order is not significant.
-__device__ __forceinline__ uint32_t esc_mask16(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
-  static_assert(S_B_ESC == 1u, "esc_mask16 tests for the byte 0x01");
-  const uint32_t w[4] = {w0, w1, w2, w3};
-  uint32_t m = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const uint32_t x = w[i] ^ 0x01010101u;
-    const uint32_t e = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;  // bit 7 of each zero byte
-    m |= e >> (7 - i);
-  }
-  return m;
-}
-__device__ __forceinline__ int esc_cell(int p) { return ((p & 7) << 2) | (p >> 3); }
-
-// exclusive prefix of v over the LPR aligned lanes of this lane's row, and the row total;
-// every lane of the row is active (the callers branch on row-uniform conditions only)
-template <int LPR>
-__device__ __forceinline__ int row_scan(int v, int li, int lane, int &total) {
-  int x = v;
-  if (LPR == 64) {
-    x = dpp_scan(v);
-    total = __builtin_amdgcn_readlane(x, 63);
-  } else {
-#pragma unroll
-    for (int o = 1; o < LPR; o <<= 1) {
-      const int y = __shfl_up(x, o, 64);
-      if (li >= o) x += y;
-    }
-    total = __shfl(x, lane - li + LPR - 1, 64);
-  }
-  return x - v;
-}
-
-// any lane of this lane's row
-template <int LPR>
-__device__ __forceinline__ bool row_any(bool p, int sub) {
-  const uint64_t b = __builtin_amdgcn_ballot_w64(p);
-  return LPR == 64 ? b != 0 : ((b >> (sub * LPR)) & ((1ull << LPR) - 1)) != 0;
-}
-
-// stripe of the (band, row) list at slab + r (gm_scaled.h: striped pool allocation)
-__device__ __forceinline__ int esc_stripe(const SState &s, size_t slab, int r) {
-  return (int)((slab + (size_t)r) & (size_t)(s.esc_stripes - 1));
-}
-// The escape-list word of a (band, row) list of `total` escaped cells written at tick parity
-// par: up to S_ESC_IN entries need no allocation; beyond, one reservation (the row's first lane)
-// in its stripe's pool region, broadcast to the row -- 0 with GM_ERR_ESC if the region overflowed
-// (the run is void). total is row-uniform.
-template <int LPR>
-__device__ __forceinline__ uint32_t row_alloc(const SState &s, int par, size_t slab, int r, int total, int li,
-                                              int lane) {
-  if (total <= S_ESC_IN) return (uint32_t)total;
-  uint32_t w = 0;
-  if (li == 0) {
-    const int stripe = esc_stripe(s, slab, r);
-    const unsigned long long need = (unsigned long long)(total - S_ESC_IN);
-    const unsigned long long b = atomicAdd(s.tesc_cnt + par * s.esc_stripes + stripe, need);
-    if (b + need <= (unsigned long long)s.tesc_region) w = (uint32_t)total | ((uint32_t)b << 11);
-    else atomicOr(s.err, GM_ERR_ESC);
-  }
-  return LPR == 64 ? __builtin_amdgcn_readfirstlane(w) : (uint32_t)__shfl((int)w, lane - li, 64);
-}
-// a list's storage: entry i < S_ESC_IN in the inline slot, the rest in its stripe's pool region
-struct EscList {
-  uint32_t *inl, *pool;
-  __device__ __forceinline__ uint32_t *at(int i) const { return i < S_ESC_IN ? inl + i : pool + (i - S_ESC_IN); }
-};
-__device__ __forceinline__ EscList esc_list(const SState &s, int par, size_t slab, int r, uint32_t word) {
-  EscList l;
-  l.inl = s.tesc_in[par] + (slab + (size_t)r) * S_ESC_IN;
-  l.pool = s.tesc[par] + (size_t)esc_stripe(s, slab, r) * s.tesc_region + S_EW_OFF(word);
-  return l;
-}
-
-// LDS of the band kernel: 32 B per lane (its 16 working cells), i.e. one wave's rows' cells in
-// column order -- the meeting point of escape entries and the lanes holding their columns
-#define S_LDS_WAVE_WORDS (64 * 8)
-__device__ __forceinline__ void lds_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Reader: the row's list (tot entries, row-uniform) into the lanes' cells: every lane of the
-// row parks its 16 cells in LDS, the row's lanes scatter the entries by column (lane li < 16
-// has entry li prefetched in `ent`; entries beyond S_ESC_IN load here), then every lane takes
-// its cells back. lds = this wave's area.
-template <int LPR>
-__device__ __forceinline__ void esc_apply(uint32_t *lds, int lane, int li, const EscList &l, int tot, uint32_t ent,
-                                          u16x2 tw[8]) {
-  u32x4 *mine = (u32x4 *)(lds + lane * 8);
-  mine[0] = (u32x4){unpk(tw[0]), unpk(tw[1]), unpk(tw[2]), unpk(tw[3])};
-  mine[1] = (u32x4){unpk(tw[4]), unpk(tw[5]), unpk(tw[6]), unpk(tw[7])};
-  lds_wave_sync();
-  uint16_t *row = (uint16_t *)(lds + (lane - li) * 8);  // the row's B cells in column order
-  constexpr int P = LPR < S_ESC_IN ? LPR : S_ESC_IN;  // entries prefetched (one per lane)
-  if (li < min(tot, P)) row[ent & 0xFFFFu] = (uint16_t)(ent >> 16);
-  for (int i = P + li; i < tot; i += LPR) {  // rare: lists longer than the prefetch
-    const uint32_t e = *l.at(i);
-    row[e & 0xFFFFu] = (uint16_t)(e >> 16);
-  }
-  lds_wave_sync();
-  const u32x4 a = mine[0], b = mine[1];
-  tw[0] = pk(a.x); tw[1] = pk(a.y); tw[2] = pk(a.z); tw[3] = pk(a.w);
-  tw[4] = pk(b.x); tw[5] = pk(b.y); tw[6] = pk(b.z); tw[7] = pk(b.w);
-}
-
-// Writer: the lane's 16 swept cells wait in its LDS slot (esc_park, right after the sweep, so
-// they need no registers through the stores); its escaped cells (mask em, esc_mask16's bit order)
-// become entries eoff, eoff + 1, ... of the list, a set bit's cell one dynamic LDS read (no
-// register indexing).
-// colb = the lane's first column in the band.
-__device__ __forceinline__ void esc_park(uint32_t *lds, int lane, const uint32_t cw[8]) {
-  u32x4 *mine = (u32x4 *)(lds + lane * 8);
-  mine[0] = (u32x4){cw[0], cw[1], cw[2], cw[3]};
-  mine[1] = (u32x4){cw[4], cw[5], cw[6], cw[7]};
-}
-// inl_only (row-uniform): the list fits its inline slot, so no entry needs the pool address.
-// An escaped cell that is present with h < hmin (3: h <= 2, its next re-base would wrap) sets
-// GM_ERR_LAG; only escaped cells can be that low (a stored byte holds h >= 226)
-__device__ __forceinline__ void esc_emit(uint32_t *lds, int lane, const EscList &l, int eoff, uint32_t em, int colb,
-                                         bool inl_only, uint32_t *err, int hmin) {
-  if (!em) return;
-  const uint16_t *cells = (const uint16_t *)(lds + lane * 8);
-  int j = eoff;
-  bool low = false;
-  for (uint32_t m = em; m; m &= m - 1) {
-    const int q = esc_cell(__builtin_ctz(m));
-    const uint32_t c = cells[q];
-    low |= c < (uint32_t)S_CELL(hmin, 0);
-    *(inl_only ? l.inl + j : l.at(j)) = (uint32_t)(colb + q) | (c << 16);
-    j++;
-  }
-  if (low) atomicOr(err, GM_ERR_LAG);
-}
-
 // Payload nibbles (gm_scaled.h S_NIB_*): dword w of a lane's 8-byte slice holds cells
 // 8w..8w+7; cell 8w+2k sits in nibble 3-k of the low u16, cell 8w+2k+1 in nibble 3-k
 // of the high u16. So v_pk_max_u16 of the dword shifted left by 4k leaves, in the top
@@ -381,7 +168,6 @@ __device__ __forceinline__ uint32_t nib_of(uint32_t x0, uint32_t x1, int q) {
   const int c = q & 7;
   return (x >> (16 * (c & 1) + 4 * (3 - (c >> 1)))) & 15u;
 }
-#define S_PESC_NONE 0xFFFFFFFFu  // payload escape record: no slots (overflow)
 // escaped payload byte h' of lane li's cell q in sender sn's slice of tick parity pp: the
 // sender's escaping lanes hold consecutive 16-byte slots from its record's base, in lane order
 __device__ __forceinline__ uint32_t pesc_value(const SState &s, int pp, int band, int sn, int li, int q) {
@@ -440,22 +226,6 @@ __device__ __forceinline__ uint64_t s_keep_nibbles(const SState &s, int t, int s
 }
 // bit 4i set where nibble i of x is non-zero
 __device__ __forceinline__ uint32_t nz_nibble_bits(uint32_t x) { return (x | (x >> 1) | (x >> 2) | (x >> 3)) & 0x11111111u; }
-
-// One work unit of the band sweep: unit u = (band u / U, rows [(u % U) * RPW, +RPW)).
-// unit_load issues the row metadata and the table slice; unit_gather the payload slices
-// (needs the sender ids); unit_finish merges, sweeps, stores and records the counts.
-template <int B>
-struct UnitIn {
-  int band, r, k;  // k: lists delivered to this lane's row, -1 = not merged (crashed / absent / not in the group)
-  int snd[S_SB];
-  u32x4 ta;        // the row's 16 cell bytes of this lane (as loaded)
-  uint32_t ebase;  // the row slice's escape list in the pool of tick t-1 (S_PESC_NONE: none)
-  uint32_t bz;     // the (band, row) record's count word of tick t-1 (S_BC_PRES: present cells as loaded)
-  uint64_t evc;    // evcum of the (row, band) as of tick t-1 (uni: read by unit_load)
-  bool uni;        // the fast path's unit: its evcum cell is written back plainly, not by an atomic
-  const uint8_t *msg;     // s.msg and the inline escape entries of tick t-1, read with the row's
-  const uint32_t *tesc;   // kernel-argument words (unit_load)
-};
 
 // the unit's table slice (this lane's 16 cell bytes); r >= n: out of range -> zeros
 template <int B>
@@ -525,36 +295,6 @@ __device__ __forceinline__ void unit_gather(const SState &s, int t, const UnitIn
 #pragma unroll
   for (int j = 0; j < S_SB; j++)
     m[j] = __builtin_amdgcn_raw_buffer_load_b64(prs, j < k ? poff + (uint32_t)in.snd[j] * B : GM_OOB, 0, 0);
-}
-
-// The unit's commit, shared by both paths of unit_finish. unit_stores (a merged row's lanes): the
-// swept slice's table bytes and payload nibbles, and its escape list; returns the list's word.
-template <int B>
-__device__ __forceinline__ uint32_t unit_stores(const SState &s, int t, const UnitIn<B> &in, const uint32_t bw[4],
-                                                uint32_t ov0, uint32_t ov1, bool esc_row, uint32_t em, uint32_t *lds) {
-  constexpr int LPR = B / S_COLS_PER_LANE;  // lanes per row
-  constexpr int Q = S_COLS_PER_LANE;        // cells per lane
-  const int lane = threadIdx.x & 63;
-  const int par = t & 1;
-  const int li = lane % LPR;
-  const int band = in.band, r = in.r;
-  const size_t slab = (size_t)band * s.n;
-  const __amdgpu_buffer_rsrc_t trs = gm_rsrc(s.table + slab * B, (uint32_t)(s.n * B));
-  const __amdgpu_buffer_rsrc_t prs = gm_rsrc(s.msg + slab * B, (uint32_t)(s.n * B));
-  const uint32_t toff = (uint32_t)(r * B + li * Q);  // bytes
-  uint32_t eb_out = 0;
-  const u32x4 nb4 = {bw[0], bw[1], bw[2], bw[3]};
-  __builtin_amdgcn_raw_buffer_store_b128(nb4, trs, toff, 0, GM_AUX_NT);
-  const u32x2 ov = {ov0, ov1};
-  __builtin_amdgcn_raw_buffer_store_b64(ov, prs, (uint32_t)(r * B + par * (B / 2) + li * 8), 0, GM_AUX_NT);
-  if (band == 0 && li == 0) s.wtick[r] = t;
-  if (esc_row) {  // the escaped cells as entries of this tick's list (the record's .w)
-    int etot;
-    const int eoff = row_scan<LPR>(__builtin_popcount(em), li, lane, etot);
-    eb_out = row_alloc<LPR>(s, par, slab, r, etot, li, lane);
-    if (eb_out != 0) esc_emit(lds, lane, esc_list(s, par, slab, r, eb_out), eoff, em, li * Q, etot <= S_ESC_IN, s.err, s.lag_hmin);
-  }
-  return eb_out;
 }
 
 // unit_records (every lane): the (band, row) record (rank-select chunk counts, the row's present /
@@ -878,29 +618,8 @@ __device__ __forceinline__ void unit_finish(const SState &s, int t, int drop_pct
     // escaped cells send the escape nibble 15 (their byte h' goes to the payload's wide plane).
     u16x2 np2 = (u16x2)(0), nf2 = (u16x2)(0), badv = (u16x2)(0), nmx = (u16x2)(0), amax = (u16x2)(0);
     u16x2 nwv[2] = {(u16x2)(0), (u16x2)(0)};
-    uint32_t cw[8], bw[4], bprev = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const u16x2 v = mm[i];
-      const u16x2 a = v & (u16x2)(31);
-      const u16x2 stale = (a + (u16x2)(32 - GM_TFAIL)) >> (u16x2)(5);  // age >= TFAIL
-      amax = __builtin_elementwise_max(amax, a);  // TREMOVE removals (rare) are applied below
-      const u16x2 pres = pmin1(v);
-      nf2 = padd(nf2, stale);
-      np2 = padd(np2, pres);
-      u16x2 bad;
-      const u16x2 b = narrow2(v, pres, bad);
-      // payload nibble of the fresh present cells: h4 - 1, or 15 where that is 0 (h4 <= 1)
-      const u16x2 p = __builtin_elementwise_sub_sat(pres, stale);
-      const u16x2 qn = __builtin_elementwise_sub_sat(b >> (u16x2)(4), (u16x2)(1));
-      const u16x2 nib = p * (__builtin_elementwise_sub_sat((u16x2)(1), qn) * (u16x2)(S_NIB_ESC) + qn);
-      nwv[i >> 2] = nwv[i >> 2] + nib * (u16x2)(1u << (4 * (3 - (i & 3))));
-      badv |= bad;
-      nmx = __builtin_elementwise_max(nmx, nib);
-      cw[i] = unpk(v);
-      if (i & 1) bw[i >> 1] = __builtin_amdgcn_perm(unpk(b), bprev, 0x06040200u);
-      else bprev = unpk(b);
-    }
+    uint32_t cw[8], bw[4];
+    sweep_cells(mm, np2, nf2, badv, nmx, amax, nwv, cw, bw);  // (gm_scaled.h: shared with the state loader)
     int ngone = 0;
     uint32_t gmask = 0;  // lane cells removed this tick (bit q = cell q)
     if (__builtin_elementwise_max(amax.x, amax.y) >= GM_TREMOVE) {
@@ -935,33 +654,8 @@ __device__ __forceinline__ void unit_finish(const SState &s, int t, int drop_pct
       }
     }
     const bool pesc = __builtin_elementwise_max(nmx.x, nmx.y) == S_NIB_ESC;
-    if (row_any<LPR>(pesc, sub)) {
-      // rare: the escaping lanes' 16 payload bytes h' into consecutive slots of this tick's payload
-      // pool (read where a receiver meets nibble 15), one reservation per row
-      const uint64_t bal = __builtin_amdgcn_ballot_w64(pesc);
-      const uint64_t rm = LPR == 64 ? bal : (bal >> (sub * LPR)) & ((1ull << LPR) - 1);
-      uint32_t pbase = S_PESC_NONE;
-      if (li == 0) {
-        const int ps = esc_stripe(s, slab, r);
-        const unsigned long long b = atomicAdd(s.pesc_cnt + par * s.esc_stripes + ps, (unsigned long long)__builtin_popcountll(rm));
-        if (b + (unsigned long long)__builtin_popcountll(rm) <= (unsigned long long)s.pesc_region)
-          pbase = (uint32_t)ps * s.pesc_region + (uint32_t)b;
-        else atomicOr(s.err, GM_ERR_ESC);
-        s.pesc_rec[par][slab + r] = make_uint4(pbase, (uint32_t)rm, (uint32_t)(rm >> 32), 0u);
-      }
-      pbase = LPR == 64 ? __builtin_amdgcn_readfirstlane(pbase) : (uint32_t)__shfl((int)pbase, lane - li, 64);
-      uint32_t pw[8];
-#pragma unroll
-      for (int i = 0; i < 8; i++) {  // removed cells send nothing: the swept cells suffice
-        const u16x2 v = pk(cw[i]);
-        const u16x2 stale = ((v & (u16x2)(31)) + (u16x2)(32 - GM_TFAIL)) >> (u16x2)(5);
-        pw[i] = unpk(__builtin_elementwise_sub_sat(v >> (u16x2)(5), stale * (u16x2)(255) + (u16x2)(2)));
-      }
-      const u32x4 wv = {__builtin_amdgcn_perm(pw[1], pw[0], 0x06040200u), __builtin_amdgcn_perm(pw[3], pw[2], 0x06040200u),
-                        __builtin_amdgcn_perm(pw[5], pw[4], 0x06040200u), __builtin_amdgcn_perm(pw[7], pw[6], 0x06040200u)};
-      if (pesc && pbase != S_PESC_NONE)
-        *(u32x4 *)(s.pesc[par] + ((size_t)pbase + __builtin_popcountll(rm & ((1ull << li) - 1))) * 16) = wv;
-    }
+    // rare: the escaping lanes' payload bytes h' go to this tick's payload pool
+    if (row_any<LPR>(pesc, sub)) payload_escapes<LPR>(s, par, slab, r, li, lane, sub, pesc, cw);
     nfail = (int)nf2.x + (int)nf2.y;
     npres = (int)np2.x + (int)np2.y;
     // joins: present after the merge (npres + ngone) but not as loaded (npb) -- the merge never

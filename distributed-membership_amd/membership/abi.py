@@ -51,7 +51,8 @@ EXPORTS = ["gm_detect_record", "gm_detect", "gm_detect_timeline", "gm_parse_conf
            "gm_comm_unique_id", "gm_comm_init", "gm_shard_layout", "gm_shard_merge", "gm_shard_draw",
            "gm_shard_accept", "gm_shard_end_tick", "gm_shard_loopback", "gm_partial_loopback_tick",
            "gm_shard_exchange_bytes", "gm_keep_events", "gm_event_totals", "gm_read_views", "gm_shard_stub",
-           "gm_msgcount_record", "gm_comm_info", "gm_shard_export", "gm_shard_import", "gm_pool_info", "gm_shard_loopback_tick", "gm_read_targets"]
+           "gm_msgcount_record", "gm_comm_info", "gm_shard_export", "gm_shard_import", "gm_pool_info", "gm_shard_loopback_tick", "gm_read_targets",
+           "gm_load_begin", "gm_load_rows", "gm_load_commit", "gm_load_stats"]
 
 _lib = None
 
@@ -104,6 +105,9 @@ def load_library():
         "gm_shard_exchange_bytes": [ctypes.c_void_p, P(ctypes.c_int64)],
         "gm_shard_merge": [ctypes.c_void_p], "gm_shard_draw": [ctypes.c_void_p, i32, i32],
         "gm_shard_accept": [ctypes.c_void_p, i32, P(i32)], "gm_shard_end_tick": [ctypes.c_void_p],
+        "gm_load_begin": [ctypes.c_void_p, i32], "gm_load_rows": [ctypes.c_void_p, i32, i32, P(i32), P(i32)],
+        "gm_load_commit": [ctypes.c_void_p, P(i32), P(i32), P(i32), P(i32)],
+        "gm_load_stats": [ctypes.c_void_p, P(ctypes.c_double)],
     }
     # GM_AB_BUILD=1 (A/B scripts only): an older measurement build may lack newer entry points, which
     # are then left unbound. Otherwise every entry point must be present, whatever library GM_LIBRARY
@@ -313,6 +317,35 @@ class Simulator:
         cnt = np.zeros(self.n, dtype=np.int32)
         self._call("gm_read_targets", self.h, _ptr(tg), _ptr(cnt))
         return tg, cnt
+
+    def load_state(self, t, hb, ts, heartbeat, failed, targets, counts, chunk_rows=None):
+        """SCALED: replace the whole state between two ticks (gm_load_begin / gm_load_rows /
+        gm_load_commit; the argument order of the oracle's load_state). hb / ts are int32 [n][w]
+        over this context's columns (a shard: its own), -1 = absent, as read_table returns them;
+        heartbeat / failed [n]; targets [n][5] and counts [n] as read_targets returns them; t is the
+        next tick to run. Rows go to the device in blocks of chunk_rows (default: about 64 MiB)."""
+        i32 = np.int32
+        w = self.shard_layout()[1]
+        hb = np.ascontiguousarray(hb, dtype=i32).reshape(self.n, w)
+        ts = np.ascontiguousarray(ts, dtype=i32).reshape(self.n, w)
+        hbt = np.ascontiguousarray(heartbeat, dtype=i32).reshape(self.n)
+        fl = np.ascontiguousarray(failed, dtype=i32).reshape(self.n)
+        tg = np.ascontiguousarray(targets, dtype=i32).reshape(self.n, 5)
+        cnt = np.ascontiguousarray(counts, dtype=i32).reshape(self.n)
+        if chunk_rows is None:
+            chunk_rows = max(1, (64 << 20) // (8 * w))
+        self._call("gm_load_begin", self.h, int(t))
+        for r0 in range(0, self.n, chunk_rows):
+            m = min(chunk_rows, self.n - r0)
+            self._call("gm_load_rows", self.h, r0, m, _ptr(hb[r0:r0 + m]), _ptr(ts[r0:r0 + m]))
+        self._call("gm_load_commit", self.h, _ptr(hbt), _ptr(fl), _ptr(tg), _ptr(cnt))
+
+    def load_stats(self):
+        """{"rows", "staging_bytes", "check_ms", "encode_ms"} of the last load (kernel times only
+        while set_timing is on)"""
+        v = (ctypes.c_double * 4)()
+        self._call("gm_load_stats", self.h, v)
+        return {"rows": int(v[0]), "staging_bytes": int(v[1]), "check_ms": float(v[2]), "encode_ms": float(v[3])}
 
     def dump_tables(self):
         n = ctypes.c_size_t()

@@ -236,6 +236,42 @@ int gm_read_nodes(gm_ctx *ctx, int32_t *state4);
  * MP1Node.cpp:449-489, as node indices; [n][5], unused slots 0) and their counts [n] -- with the
  * tables and node state, the whole state between two ticks */
 int gm_read_targets(gm_ctx *ctx, int32_t *targets, int32_t *counts);
+/* ---- SCALED: load a cluster state into a context, the inverse of gm_read_table / gm_read_nodes /
+ * gm_read_targets (the oracle's oc_load_scaled, oracle/ref_cpu.c). The state between two ticks is
+ * layout-independent, so a state read from a context of any band width, from column shards, or from
+ * the oracle loads into any other. Contexts created with init_mode 0 or 1 only: FAITHFUL, PARTIAL,
+ * join-ramp contexts and contexts recording msgcount return GM_EUNSUPPORTED. A column shard loads its
+ * own columns [c0, c0 + w) and the same node arrays as every other shard.
+ *
+ * gm_load_begin settles the run so far, allocates a device staging buffer (<= 512 MiB whatever n is;
+ * the commit frees it) and puts the context into the loading state: until gm_load_commit succeeds,
+ * gm_tick, the shard phase calls and gm_set_failed return GM_ESTATE and the read-back functions are
+ * undefined. t >= 1 is the next tick to run.
+ * gm_load_rows gives rows [r0, r0 + count): hb / ts [count][w] over this context's w columns, -1 =
+ * absent -- exactly what gm_read_table(r0, count) returns. Blocks in any order, each row exactly once
+ * (a repeat, or a commit with rows missing: GM_ESTATE). The block is staged and encoded on the device.
+ * gm_load_commit gives the heartbeat counters, crash flags (0 / 1), last tick's gossip targets [n][5]
+ * and their counts [n] (0..5), builds the inboxes of tick t from them and sets the time to t. The
+ * context is then as tick t - 1 would have left it: no pending events (gm_drain_events returns none,
+ * gm_event_counts 0), the error flag clear. gm_event_totals and a detection recorder carry on.
+ *
+ * Everything is checked on the device before it is written. GM_EINVAL: ts > t - 1; one of hb / ts
+ * negative and the other not; a heartbeat ahead of its row's tick; counts outside 0..5; a target
+ * outside [0, n); failed not 0 / 1; a live row whose own entry is not {heartbeat - 1, t - 1} (the
+ * self bump of tick t - 1; the cold start's {0, 0} with heartbeat 0 at t = 1 is the one exception);
+ * a crashed row with targets that did not run tick t - 1. GM_ERANGE: an entry whose heartbeat lag or
+ * age does not fit the cell (relative to t - 1, or for a crashed row to its newest ts); more lists
+ * for one receiver than its inbox holds; a state that overflows the escape pools. After a failed
+ * call the context stays in the loading state; gm_load_begin starts over. */
+int gm_load_begin(gm_ctx *ctx, int32_t t);
+int gm_load_rows(gm_ctx *ctx, int32_t r0, int32_t count, const int32_t *hb, const int32_t *ts);
+int gm_load_commit(gm_ctx *ctx, const int32_t *heartbeat, const int32_t *failed, const int32_t *targets,
+                   const int32_t *counts);
+/* stats = {rows encoded since the last gm_load_begin, bytes of its staging buffer, and, while
+ * gm_set_timing is on (HIP events around each launch, one wait per block), the milliseconds spent in
+ * the check kernel and in the encode kernel} */
+int gm_load_stats(gm_ctx *ctx, double stats[4]);
+
 /* Render the membership lists of every node in the parity dump format
  * ("t i inited inGroup bFailed heartbeat n id:hb:ts ...\n" per node). */
 int gm_dump_tables(gm_ctx *ctx, char *buf, size_t cap, size_t *len);
