@@ -48,6 +48,8 @@ hipError_t gm_launch_partial_reset(const PState &s, hipStream_t st);
 hipError_t gm_launch_partial_chunk(const PState &s, int t, const uint32_t *mtraw, int c, hipStream_t st);
 hipError_t gm_launch_msgcount(const SState &s, int t, bool dropped, int phase, hipStream_t st);
 hipError_t gm_launch_detect(const SState &s, gm_detect_rec *rec, uint64_t *timeline, int t, hipStream_t st);
+hipError_t gm_launch_census(const SState &s, gm_census_rec *rec, uint64_t *hist, uint32_t *status, int T,
+                            hipStream_t st);
 hipError_t gm_launch_load_check(const SState &s, int t, int r0, int cnt, const int32_t *hb, const int32_t *ts,
                                 int32_t *base, int32_t *own, uint32_t *status, hipStream_t st);
 hipError_t gm_launch_load_encode(const SState &s, int t, int r0, int cnt, const int32_t *hb, const int32_t *ts,
@@ -111,6 +113,9 @@ struct gm_ctx {
   uint64_t *det_tl = nullptr;        // device [det_tmax][3]
   std::vector<gm_detect_rec> det_h;  // FAITHFUL [n]
   std::vector<uint64_t> det_tl_h;    // FAITHFUL [det_tmax][3]
+  // SCALED census (gm_census): device scratch, allocated by the first call -- the records [s.w], the
+  // histogram, the kernels' status word
+  uint8_t *cen_blob = nullptr;
   // FAITHFUL
   FState f{};
   size_t f_smem = 0;
@@ -1427,6 +1432,35 @@ extern "C" int gm_detect_timeline(gm_ctx *c, int32_t t, uint64_t *out) {
     HIPCHECK(ctx_memcpy(c, out, c->det_tl, sizeof(uint64_t) * 3 * (size_t)t, hipMemcpyDeviceToHost));
   else
     memcpy(out, c->det_tl_h.data(), sizeof(uint64_t) * 3 * (size_t)t);
+  return GM_OK;
+}
+
+// SCALED: the census of the state as of the last tick (gm_census.hip). A read-back: it settles the
+// enqueued ticks, reports their device error, and writes nothing but its own scratch.
+extern "C" int gm_census(gm_ctx *c, gm_census_rec *out, uint64_t *hist) {
+  if (!c || (!out && !hist)) return GM_EINVAL;
+  if (c->cfg.mode != GM_MODE_SCALED) return GM_EUNSUPPORTED;
+  if (c->loading) return GM_ESTATE;  // between gm_load_begin and gm_load_commit
+  if (c->latched != GM_OK) return c->latched;
+  TRY(draw_settle(c));
+  TRY(check_err(c));  // waits for the stream
+  const SState &s = c->s;
+  const size_t rec_bytes = sizeof(gm_census_rec) * (size_t)s.w;
+  const size_t hist_bytes = sizeof(uint64_t) * 2 * GM_CENSUS_LAGS * GM_CENSUS_AGES;
+  if (!c->cen_blob) TRY(dalloc(c, &c->cen_blob, rec_bytes + hist_bytes + sizeof(uint64_t)));
+  gm_census_rec *d_rec = (gm_census_rec *)c->cen_blob;
+  uint64_t *d_hist = (uint64_t *)(c->cen_blob + rec_bytes);
+  uint32_t *d_status = (uint32_t *)(c->cen_blob + rec_bytes + hist_bytes);
+  HIPCHECK(ctx_memset(c, c->cen_blob, 0, rec_bytes + hist_bytes + sizeof(uint64_t)));
+  HIPCHECK(gm_launch_census(s, d_rec, d_hist, d_status, c->t - 1, c->stream));
+  uint32_t st = 0;
+  HIPCHECK(ctx_memcpy(c, &st, d_status, sizeof st, hipMemcpyDeviceToHost));
+  if (st) {
+    snprintf(g_errbuf, sizeof g_errbuf, "gm_census: the stored state is inconsistent (flags 0x%x)", st);
+    return GM_ESTATE;
+  }
+  if (out) HIPCHECK(ctx_memcpy(c, out, d_rec, rec_bytes, hipMemcpyDeviceToHost));
+  if (hist) HIPCHECK(ctx_memcpy(c, hist, d_hist, hist_bytes, hipMemcpyDeviceToHost));
   return GM_OK;
 }
 

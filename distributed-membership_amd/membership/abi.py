@@ -45,6 +45,18 @@ DETECT_DTYPE = np.dtype([("fail_tick", "<i4"), ("first_removed", "<i4"), ("last_
                          ("removed_tick_sum", "<u8")])
 assert DETECT_DTYPE.itemsize == ctypes.sizeof(GmDetectRec) == 32
 
+class GmCensusRec(ctypes.Structure):
+    _fields_ = [("hb_min", ctypes.c_int32), ("hb_max", ctypes.c_int32), ("ts_min", ctypes.c_int32),
+                ("ts_max", ctypes.c_int32), ("holders", ctypes.c_uint32), ("stale", ctypes.c_uint32),
+                ("hb_sum", ctypes.c_uint64), ("ts_sum", ctypes.c_uint64)]
+
+
+# gm_census_rec as a NumPy structured dtype (40 bytes, the field names of include/gm_abi.h)
+GM_CENSUS_LAGS, GM_CENSUS_AGES = 64, 32
+CENSUS_DTYPE = np.dtype([("hb_min", "<i4"), ("hb_max", "<i4"), ("ts_min", "<i4"), ("ts_max", "<i4"),
+                         ("holders", "<u4"), ("stale", "<u4"), ("hb_sum", "<u8"), ("ts_sum", "<u8")])
+assert CENSUS_DTYPE.itemsize == ctypes.sizeof(GmCensusRec) == 40
+
 EXPORTS = ["gm_detect_record", "gm_detect", "gm_detect_timeline", "gm_parse_conf", "gm_create", "gm_destroy", "gm_tick", "gm_sync", "gm_time", "gm_rand", "gm_set_failed",
            "gm_set_dropmsg", "gm_drain_events", "gm_event_counts", "gm_msgcount", "gm_read_row", "gm_read_table", "gm_read_nodes",
            "gm_dump_tables", "gm_tick_stats", "gm_set_timing", "gm_last_kernel_ms", "gm_crash_set", "gm_strerror",
@@ -52,7 +64,7 @@ EXPORTS = ["gm_detect_record", "gm_detect", "gm_detect_timeline", "gm_parse_conf
            "gm_shard_accept", "gm_shard_end_tick", "gm_shard_loopback", "gm_partial_loopback_tick",
            "gm_shard_exchange_bytes", "gm_keep_events", "gm_event_totals", "gm_read_views", "gm_shard_stub",
            "gm_msgcount_record", "gm_comm_info", "gm_shard_export", "gm_shard_import", "gm_pool_info", "gm_shard_loopback_tick", "gm_read_targets",
-           "gm_load_begin", "gm_load_rows", "gm_load_commit", "gm_load_stats"]
+           "gm_load_begin", "gm_load_rows", "gm_load_commit", "gm_load_stats", "gm_census"]
 
 _lib = None
 
@@ -108,6 +120,7 @@ def load_library():
         "gm_load_begin": [ctypes.c_void_p, i32], "gm_load_rows": [ctypes.c_void_p, i32, i32, P(i32), P(i32)],
         "gm_load_commit": [ctypes.c_void_p, P(i32), P(i32), P(i32), P(i32)],
         "gm_load_stats": [ctypes.c_void_p, P(ctypes.c_double)],
+        "gm_census": [ctypes.c_void_p, P(GmCensusRec), P(u64)],
     }
     # GM_AB_BUILD=1 (A/B scripts only): an older measurement build may lack newer entry points, which
     # are then left unbound. Otherwise every entry point must be present, whatever library GM_LIBRARY
@@ -288,6 +301,18 @@ class Simulator:
         out = np.zeros((t, 3), dtype=np.uint64)
         self._call("gm_detect_timeline", self.h, t, _ptr(out, ctypes.c_uint64))
         return out
+
+    def census(self, records=True, hist=True):
+        """SCALED: the membership census of the state as of the last tick, reduced on the device
+        (gm_census). Returns (rec, hist): rec a CENSUS_DTYPE array, one record per subject column of
+        this context (holders, stale, hb / ts min, max and sums over the live observers' entries);
+        hist uint64 [2, 64, 32], the live observers' cells by (subject's crash flag, heartbeat lag
+        clipped to 63, age). The half not asked for is None."""
+        rec = np.zeros(self.shard_layout()[1], dtype=CENSUS_DTYPE) if records else None
+        h = np.zeros((2, GM_CENSUS_LAGS, GM_CENSUS_AGES), dtype=np.uint64) if hist else None
+        self._call("gm_census", self.h, rec.ctypes.data_as(ctypes.POINTER(GmCensusRec)) if records else None,
+                   _ptr(h, ctypes.c_uint64) if hist else None)
+        return rec, h
 
     def read_row(self, r, c0=0, length=None):
         length = self.n if length is None else length

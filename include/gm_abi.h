@@ -272,6 +272,28 @@ int gm_load_commit(gm_ctx *ctx, const int32_t *heartbeat, const int32_t *failed,
  * the check kernel and in the encode kernel} */
 int gm_load_stats(gm_ctx *ctx, double stats[4]);
 
+/* ---- SCALED: the membership census, reduced on the device (the table is not copied to the host). */
+#define GM_CENSUS_LAGS 64
+#define GM_CENSUS_AGES 32
+typedef struct gm_census_rec {   /* 40 bytes, one per subject column of this context */
+  int32_t  hb_min, hb_max;       /* over the entries counted in holders; -1 = none */
+  int32_t  ts_min, ts_max;       /* -1 = none */
+  uint32_t holders;              /* live observers (failed == 0) whose table holds the subject */
+  uint32_t stale;                /* of those, entries with T - ts >= TFAIL (what numfailed counts) */
+  uint64_t hb_sum, ts_sum;       /* sums over the holders' entries */
+} gm_census_rec;
+/* SCALED. The state as of the last tick run, T = gm_time - 1 (after create or gm_load_commit: as
+ * created / loaded). out[w] over this context's columns [c0, c0 + w) (gm_shard_layout);
+ * hist[2][GM_CENSUS_LAGS][GM_CENSUS_AGES]: cells of live observers by (subject's failed flag,
+ * lag = (2T - hb) >> 1 clipped to GM_CENSUS_LAGS - 1, age = T - ts). Either pointer may be NULL, not both.
+ * (hb, ts) of a cell are what gm_read_table returns for it; rows with failed != 0 (frozen tables)
+ * contribute nothing, a live observer's own entry counts. A column shard reports its own columns; the
+ * shards' histograms add up to the cluster's. Join-ramp contexts are supported. The call is a
+ * read-back: it waits for the enqueued ticks, reports a latched device error and changes nothing a
+ * later tick or read observes. FAITHFUL / PARTIAL: GM_EUNSUPPORTED; while loading: GM_ESTATE; a
+ * stored state whose escape lists disagree with its cells: GM_ESTATE. */
+int gm_census(gm_ctx *ctx, gm_census_rec *out, uint64_t *hist);
+
 /* Render the membership lists of every node in the parity dump format
  * ("t i inited inGroup bFailed heartbeat n id:hb:ts ...\n" per node). */
 int gm_dump_tables(gm_ctx *ctx, char *buf, size_t cap, size_t *len);
