@@ -38,8 +38,6 @@ hipError_t gm_launch_accept(const SState &s, int t, int D, int in_list, int out,
                             int r1 = -1);
 hipError_t gm_launch_plist_sort(const SState &s, int l, hipStream_t st);
 hipError_t gm_launch_init(const SState &s, int warm, int t0, uint64_t seed, hipStream_t st);
-hipError_t gm_launch_partial_tick(const PState &s, int t, uint32_t *mtraw, hipStream_t st, hipEvent_t k0,
-                                  hipEvent_t k1);
 hipError_t gm_launch_partial_init(const PState &s, int t0, uint64_t init_seed, hipStream_t st);
 hipError_t gm_launch_partial_unpack(const PState &s, int t, int base, int nrecv, hipStream_t st);
 hipError_t gm_launch_partial_pack(const PState &s, int t, int c, hipStream_t st);
@@ -894,13 +892,13 @@ static int f_collect(gm_ctx *c) {
   return c->latched;
 }
 
-static int draw_settle(gm_ctx *c);
+static int draw_settle(gm_ctx **g, int G);
 
 // Everything that reads the state (records, tables, counters, the S1 stream) or starts the
 // next tick first completes the enqueued ticks: FAITHFUL collects its mailboxes; a column
 // shard finishes the draws its bounded rounds left (rare).
 static int f_settle(gm_ctx *c) {
-  return c->cfg.mode == GM_MODE_FAITHFUL ? f_collect(c) : c->cfg.mode == GM_MODE_SCALED ? draw_settle(c) : GM_OK;
+  return c->cfg.mode == GM_MODE_FAITHFUL ? f_collect(c) : c->cfg.mode == GM_MODE_SCALED ? draw_settle(&c, 1) : GM_OK;
 }
 
 // FAITHFUL ticks are enqueued without a host wait: the records stay on the device until a
@@ -934,14 +932,20 @@ static int tick_faithful(gm_ctx *c) {
   return c->latched;
 }
 
-static int tick_sharded(gm_ctx *c);
+// A sharded tick is written once, over a GROUP of local ranks (gm_ctx **g, count G): gm_tick passes
+// {c} (its peers are RCCL ranks, or none under gm_shard_stub), the loopback entry points the G
+// contexts of one cluster living on one device. A tick is a sequence of steps "every member
+// enqueues this launch" separated by group collectives (grp_*, px_*), the only code that differs by
+// group kind. Streams and events are the first member's; buffers and host bookkeeping each member's.
+static int tick_sharded(gm_ctx **g, int G);
 static int before_tick_events(gm_ctx *c);
+static bool drop_tick(const gm_ctx *c, int t);
 
-// Tick-kernel timing: a ring of GM_TEV_RING event pairs on the context stream; a slot
+// Tick-kernel timing: a ring of GM_TEV_RING event pairs on the tick's stream; a slot
 // is folded into kernel_ms_sum when it is reused (its tick finished long before).
 #define GM_TEV_RING 64
-static int timing_slot(gm_ctx *c, hipEvent_t *k0, hipEvent_t *k1) {
-  if (c->timed_ticks == 0) HIPCHECK(hipEventRecord(c->e0, c->stream));
+static int timing_slot(gm_ctx *c, hipEvent_t *k0, hipEvent_t *k1, hipStream_t st) {
+  if (c->timed_ticks == 0) HIPCHECK(hipEventRecord(c->e0, st));
   while (c->tev.size() < 2 * (size_t)GM_TEV_RING) {
     hipEvent_t e;
     HIPCHECK(hipEventCreate(&e));
@@ -961,7 +965,7 @@ static int timing_slot(gm_ctx *c, hipEvent_t *k0, hipEvent_t *k1) {
 }
 
 // Join ramp: nodeStart of this tick's starters clears bFailed (MP1Node.cpp:108)
-static int ramp_starters(gm_ctx *c) {
+static int ramp_starters(gm_ctx *c, hipStream_t st) {
   if (!c->s.ramp) return GM_OK;
   const int j0 = 4 * c->t, j1 = std::min(c->n, 4 * c->t + 4);
   for (int j = j0; j < j1; j++)
@@ -969,8 +973,7 @@ static int ramp_starters(gm_ctx *c) {
       c->failed_h[j] = 0;
       c->fail_t[j] = 0x7FFFFFFF;
       c->nfailed--;
-      HIPCHECK(hipMemcpyAsync(c->s.failed + j, c->failed_h.data() + j, sizeof(int32_t), hipMemcpyHostToDevice,
-                              c->stream));
+      HIPCHECK(hipMemcpyAsync(c->s.failed + j, c->failed_h.data() + j, sizeof(int32_t), hipMemcpyHostToDevice, st));
     }
   return GM_OK;
 }
@@ -986,12 +989,11 @@ static int detect_tick(gm_ctx *c, int t, hipStream_t st) {
 
 static int tick_scaled(gm_ctx *c) {
   if (c->t > GM_T_LIMIT) return GM_ERANGE;
-  if (c->s.sharded) return tick_sharded(c);
-  TRY(ramp_starters(c));
-  const int t_send = c->t - 1;
-  const bool drop = c->cfg.drop_pct > 0 && t_send >= c->cfg.drop_from && t_send < c->cfg.drop_to;
+  if (c->s.sharded) return tick_sharded(&c, 1);
+  TRY(ramp_starters(c, c->stream));
+  const bool drop = drop_tick(c, c->t);
   hipEvent_t k0 = nullptr, k1 = nullptr;
-  if (c->timing) TRY(timing_slot(c, &k0, &k1));
+  if (c->timing) TRY(timing_slot(c, &k0, &k1, c->stream));
   HIPCHECK(gm_launch_tick(c->s, c->t, drop ? c->cfg.drop_pct : -1, c->stream, k0, k1, true));
   TRY(detect_tick(c, c->t, c->stream));
   if (c->s.mc_sent && c->t < c->s.mc_tmax) {
@@ -1005,101 +1007,96 @@ static int tick_scaled(gm_ctx *c) {
   return GM_OK;
 }
 
-static int partial_exchange_chunk(gm_ctx *c, int q, int64_t *roff);
+static int px_agree(gm_ctx **g, int G, hipStream_t st);
+static int px_exchange(gm_ctx **g, int G, int ch, hipStream_t cs);
 
-static int tick_partial(gm_ctx *c) {
-  if (c->t > GM_T_LIMIT) return GM_ERANGE;
-  if (c->p_sharded && !c->comm) return GM_EUNSUPPORTED;  // row shards need gm_comm_init (or gm_partial_loopback)
-  const int t_send = c->t - 1;
-  const bool drop = c->cfg.drop_pct > 0 && t_send >= c->cfg.drop_from && t_send < c->cfg.drop_to;
-  PState st = c->p;
-  st.drop_pct = drop ? c->cfg.drop_pct : -1;
+// One PARTIAL tick of a group: an unsharded context, one RCCL row shard, or the G row shards of a
+// loopback cluster. A loopback group runs shard after shard on its first member's streams: the sum
+// of the shards' own costs (8 concurrent stream pairs on one device starve each other's small
+// worklist kernels; on a node every shard has its GPU to itself). Timing events are the first
+// member's (they bracket the whole group's kernels).
+static int tick_partial(gm_ctx **g, int G) {
+  gm_ctx *L = g[0];
+  if (L->t > GM_T_LIMIT) return GM_ERANGE;
+  if (G == 1 && L->p_sharded && !L->comm) return GM_EUNSUPPORTED;  // row shards need gm_comm_init (or gm_partial_loopback_tick)
+  hipStream_t st = L->stream;
+  const int t = L->t, par = t & 1, K = L->p.nchunk;
+  auto mt = [&](gm_ctx *c, int q) { return c->p_mtraw + (size_t)q * c->p.nloc * 16; };
   hipEvent_t k0 = nullptr, k1 = nullptr;
-  if (c->timing) TRY(timing_slot(c, &k0, &k1));
+  if (L->timing) TRY(timing_slot(L, &k0, &k1, st));
   // S2 outputs of this tick: prefetched on the side stream while the last tick ran
   // (they depend only on (seed, t, id)), else computed here
-  const int t = c->t, par = t & 1;
-  uint32_t *mt = c->p_mtraw + (size_t)par * st.nloc * 16;
-  if (c->p_mt_next == t) {
-    HIPCHECK(hipStreamWaitEvent(c->stream, c->p_mtev[par], 0));
-    HIPCHECK(gm_launch_partial_reset(st, c->stream));
-  } else {
-    HIPCHECK(gm_launch_partial_mtgen(st, t, mt, c->stream, true));
-  }
-  if (k0) HIPCHECK(hipEventRecord(k0, c->stream));
-  if (!c->p_sharded) {
-    HIPCHECK(gm_launch_partial_chunk(st, t, mt, 0, c->stream));
-    if (k1) HIPCHECK(hipEventRecord(k1, c->stream));
-  } else {
-    if (c->p_crash_check) {
-      // the block capacities (send counts of this rank, receive counts of its peers) derive from the
-      // crash set each rank was given (gm_set_failed): a rank holding another set would size its
-      // ncclAllToAllv differently and hang or corrupt it. One MAX-allreduce of (h, ~h) after each
-      // change shows any disagreement, and the context latches GM_ESTATE instead.
-      c->p_crash_check = false;
-      if (!c->p_crash_dev) {
-        HIPCHECK(hipMalloc(&c->p_crash_dev, 2 * sizeof(uint64_t)));
-        c->allocs.push_back(c->p_crash_dev);
-      }
-      uint64_t hv[2] = {c->p_crash_hash, ~c->p_crash_hash}, mx[2] = {0, 0};
-      HIPCHECK(hipMemcpyAsync(c->p_crash_dev, hv, sizeof hv, hipMemcpyHostToDevice, c->stream));
-      NCCLCHECK(ncclAllReduce(c->p_crash_dev, c->p_crash_dev, 2, ncclUint64, ncclMax, c->comm, c->stream));
-      HIPCHECK(hipMemcpyAsync(mx, c->p_crash_dev, sizeof mx, hipMemcpyDeviceToHost, c->stream));
-      HIPCHECK(hipStreamSynchronize(c->stream));
-      if (mx[0] != hv[0] || mx[1] != hv[1]) {
-        c->latched = GM_ESTATE;
-        return c->latched;
-      }
+  for (int i = 0; i < G; i++) {
+    gm_ctx *c = g[i];
+    c->p.drop_pct = drop_tick(c, t) ? c->cfg.drop_pct : -1;  // read by this tick's node kernels only
+    if (c->p_mt_next == t) {
+      HIPCHECK(hipStreamWaitEvent(st, L->p_mtev[par], 0));
+      HIPCHECK(gm_launch_partial_reset(c->p, st));
+    } else {
+      HIPCHECK(gm_launch_partial_mtgen(c->p, t, mt(c, par), st, true));
     }
+  }
+  if (k0) HIPCHECK(hipEventRecord(k0, st));
+  if (!L->p_sharded) {
+    HIPCHECK(gm_launch_partial_chunk(L->p, t, mt(L, par), 0, st));
+    if (k1) HIPCHECK(hipEventRecord(k1, st));
+  } else {
+    bool check = false;
+    for (int i = 0; i < G; i++) {
+      check |= g[i]->p_crash_check;
+      g[i]->p_crash_check = false;
+    }
+    if (check) TRY(px_agree(g, G, st));
     // chunk pipeline: every chunk's node ticks queue on the compute stream; the exchange of
     // chunk q runs on the comm stream once q's kernels are done, while q+1.. still compute
-    for (int q = 0; q < st.nchunk; q++) {
-      HIPCHECK(gm_launch_partial_chunk(st, t, mt, q, c->stream));
-      HIPCHECK(hipEventRecord(c->p_chev[q], c->stream));
+    for (int q = 0; q < K; q++) {
+      for (int i = 0; i < G; i++) HIPCHECK(gm_launch_partial_chunk(g[i]->p, t, mt(g[i], par), q, st));
+      HIPCHECK(hipEventRecord(L->p_chev[q], st));
     }
-    if (k1) HIPCHECK(hipEventRecord(k1, c->stream));
-    int64_t roff = 0;
-    for (int q = 0; q < st.nchunk; q++) {
-      HIPCHECK(hipStreamWaitEvent(c->p_comm, c->p_chev[q], 0));
-      TRY(partial_exchange_chunk(c, q, &roff));
+    if (k1) HIPCHECK(hipEventRecord(k1, st));
+    for (int q = 0; q < K; q++) {
+      HIPCHECK(hipStreamWaitEvent(L->p_comm, L->p_chev[q], 0));
+      TRY(px_exchange(g, G, q, L->p_comm));
     }
-    c->p_recv_last = roff;
-    HIPCHECK(hipEventRecord(c->p_done, c->p_comm));
-    HIPCHECK(hipStreamWaitEvent(c->stream, c->p_done, 0));  // the next tick reads the unpacked inboxes
+    HIPCHECK(hipEventRecord(L->p_done, L->p_comm));
+    HIPCHECK(hipStreamWaitEvent(st, L->p_done, 0));  // the next tick reads the unpacked inboxes
   }
   // prefetch tick t+1's S2 outputs into the other parity buffer, last read by tick t-1
-  HIPCHECK(hipEventRecord(c->p_tickev[par], c->stream));
-  HIPCHECK(hipStreamWaitEvent(c->p_side, c->p_tickev[par ^ 1], 0));
-  HIPCHECK(gm_launch_partial_mtgen(st, t + 1, c->p_mtraw + (size_t)(par ^ 1) * st.nloc * 16, c->p_side, false));
-  HIPCHECK(hipEventRecord(c->p_mtev[par ^ 1], c->p_side));
-  c->p_mt_next = t + 1;
-  if (c->timing) {
-    HIPCHECK(hipEventRecord(c->e1, c->stream));
-    c->timed_ticks++;
+  HIPCHECK(hipEventRecord(L->p_tickev[par], st));
+  HIPCHECK(hipStreamWaitEvent(L->p_side, L->p_tickev[par ^ 1], 0));
+  for (int i = 0; i < G; i++) {
+    HIPCHECK(gm_launch_partial_mtgen(g[i]->p, t + 1, mt(g[i], par ^ 1), L->p_side, false));
+    g[i]->p_mt_next = t + 1;
+  }
+  HIPCHECK(hipEventRecord(L->p_mtev[par ^ 1], L->p_side));
+  if (L->timing) {
+    HIPCHECK(hipEventRecord(L->e1, st));
+    L->timed_ticks++;
   }
   return GM_OK;
+}
+
+static void advance(gm_ctx *c) {  // a tick was enqueued: globaltime moves on
+  c->t++;
+  c->ticks_done++;
+  c->undrained = c->cfg.mode != GM_MODE_FAITHFUL;
 }
 
 extern "C" int gm_tick(gm_ctx *c) {
   if (!c) return GM_EINVAL;
   if (c->latched != GM_OK) return c->latched;
   if (c->loading) return GM_ESTATE;  // between gm_load_begin and gm_load_commit
-  if (c->cfg.mode == GM_MODE_SCALED) TRY(draw_settle(c));
+  if (c->cfg.mode == GM_MODE_SCALED) TRY(draw_settle(&c, 1));
   TRY(before_tick_events(c));
   int rc = c->cfg.mode == GM_MODE_FAITHFUL ? tick_faithful(c) : c->cfg.mode == GM_MODE_SCALED ? tick_scaled(c)
-                                                                                             : tick_partial(c);
-  if (rc == GM_OK) {
-    c->t++;
-    c->ticks_done++;
-    c->undrained = c->cfg.mode != GM_MODE_FAITHFUL;
-  }
+                                                                                             : tick_partial(&c, 1);
+  if (rc == GM_OK) advance(c);
   return rc;
 }
 
 extern "C" int gm_sync(gm_ctx *c) {
   if (!c) return GM_EINVAL;
-  TRY(f_settle(c));
-  if (c->cfg.mode == GM_MODE_SCALED) TRY(draw_settle(c));  // a sharded tick's remaining draw rounds
+  TRY(f_settle(c));  // a sharded tick's remaining draw rounds
   HIPCHECK(hipStreamSynchronize(c->stream));
   return check_err(c);
 }
@@ -1442,7 +1439,7 @@ extern "C" int gm_census(gm_ctx *c, gm_census_rec *out, uint64_t *hist) {
   if (c->cfg.mode != GM_MODE_SCALED) return GM_EUNSUPPORTED;
   if (c->loading) return GM_ESTATE;  // between gm_load_begin and gm_load_commit
   if (c->latched != GM_OK) return c->latched;
-  TRY(draw_settle(c));
+  TRY(draw_settle(&c, 1));
   TRY(check_err(c));  // waits for the stream
   const SState &s = c->s;
   const size_t rec_bytes = sizeof(gm_census_rec) * (size_t)s.w;
@@ -1814,7 +1811,7 @@ extern "C" int gm_dump_tables(gm_ctx *c, char *buf, size_t cap, size_t *len) {
 extern "C" int gm_read_targets(gm_ctx *c, int32_t *targets, int32_t *counts) {
   if (!c || !targets || !counts) return GM_EINVAL;
   if (c->cfg.mode != GM_MODE_SCALED) return GM_EUNSUPPORTED;
-  TRY(draw_settle(c));
+  TRY(draw_settle(&c, 1));
   const size_t n = (size_t)c->n;
   std::vector<int32_t> st(n * 4);
   HIPCHECK(ctx_memcpy(c, targets, c->s.targets, sizeof(int32_t) * n * GM_FANOUT, hipMemcpyDeviceToHost));
@@ -1857,7 +1854,7 @@ extern "C" int gm_load_begin(gm_ctx *c, int32_t t) {
   if (c->latched != GM_OK) return c->latched;
   SState &s = c->s;
   if (!c->loading) {  // settle the run so far; its device error, if any, is the caller's to see
-    TRY(draw_settle(c));
+    TRY(draw_settle(&c, 1));
     HIPCHECK(hipStreamSynchronize(c->stream));
     TRY(check_err(c));
   } else {
@@ -2171,21 +2168,25 @@ static int shard_ready(gm_ctx *c) {
   return GM_OK;
 }
 
+// the unchunked merge of one shard: its band kernels over every row, its row totals
+static int shard_merge(gm_ctx *c, hipStream_t st) {
+  TRY(ramp_starters(c, st));
+  const bool drop = drop_tick(c, c->t);
+  HIPCHECK(hipMemsetAsync(c->s.xcnt, 0, xcnt_bytes(c->s), st));
+  hipEvent_t k0 = nullptr, k1 = nullptr;
+  if (c->timing) TRY(timing_slot(c, &k0, &k1, st));
+  HIPCHECK(gm_launch_tick(c->s, c->t, drop ? c->cfg.drop_pct : -1, st, k0, k1, false));
+  TRY(detect_tick(c, c->t, st));
+  HIPCHECK(gm_launch_xrows(c->s, 0, c->n, st));  // this shard's row totals for the all-gather
+  // msgcount: this shard's fresh counts (its columns), SUM-allreduced before the draws
+  if (mc_on(c, c->t)) HIPCHECK(gm_launch_msgcount(c->s, c->t, drop, 0, st));
+  return GM_OK;
+}
+
 extern "C" int gm_shard_merge(gm_ctx *c) {
   TRY(shard_ready(c));
   TRY(before_tick_events(c));
-  TRY(ramp_starters(c));
-  const int t_send = c->t - 1;
-  const bool drop = c->cfg.drop_pct > 0 && t_send >= c->cfg.drop_from && t_send < c->cfg.drop_to;
-  HIPCHECK(hipMemsetAsync(c->s.xcnt, 0, xcnt_bytes(c->s), c->stream));
-  hipEvent_t k0 = nullptr, k1 = nullptr;
-  if (c->timing) TRY(timing_slot(c, &k0, &k1));
-  HIPCHECK(gm_launch_tick(c->s, c->t, drop ? c->cfg.drop_pct : -1, c->stream, k0, k1, false));
-  TRY(detect_tick(c, c->t, c->stream));
-  HIPCHECK(gm_launch_xrows(c->s, 0, c->n, c->stream));  // this shard's row totals for the all-gather
-  // msgcount: this shard's fresh counts (its columns), SUM-allreduced before the draws
-  if (mc_on(c, c->t)) HIPCHECK(gm_launch_msgcount(c->s, c->t, drop, 0, c->stream));
-  return GM_OK;
+  return shard_merge(c, c->stream);
 }
 
 extern "C" int gm_shard_draw(gm_ctx *c, int32_t round, int32_t D) {
@@ -2206,18 +2207,23 @@ extern "C" int gm_shard_accept(gm_ctx *c, int32_t D, int32_t *npending) {
   return GM_OK;
 }
 
-extern "C" int gm_shard_end_tick(gm_ctx *c) {
-  TRY(shard_ready(c));
+// The last device work of a shard's tick c->t; time does not advance here (gm_tick, the loopback
+// driver and gm_shard_end_tick do that).
+static int shard_finish(gm_ctx *c, hipStream_t st) {
   // msgcount: sent / received once the targets are final (after draw_settle when bounded
   // rounds left rows to the host-driven loop)
-  if (!c->draw_check && mc_on(c, c->t)) HIPCHECK(gm_launch_msgcount(c->s, c->t, drop_tick(c, c->t), 1, c->stream));
+  if (!c->draw_check && mc_on(c, c->t)) HIPCHECK(gm_launch_msgcount(c->s, c->t, drop_tick(c, c->t), 1, st));
   if (c->timing) {  // band-kernel events are in the timing ring (no host wait here)
-    HIPCHECK(hipEventRecord(c->e1, c->stream));
+    HIPCHECK(hipEventRecord(c->e1, st));
     c->timed_ticks++;
   }
-  c->t++;
-  c->ticks_done++;
-  c->undrained = true;
+  return GM_OK;
+}
+
+extern "C" int gm_shard_end_tick(gm_ctx *c) {
+  TRY(shard_ready(c));
+  TRY(shard_finish(c, c->stream));
+  advance(c);
   return GM_OK;
 }
 
@@ -2229,140 +2235,100 @@ __global__ void gm_add_into(uint32_t *dst, const uint32_t *src, size_t n) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
     dst[i] += src[i];
 }
-
-// In-process collectives between the G shard contexts of one device:
-// what = 0 all-gathers xcnt, what = 1 MAX-allreduces status[0, n*D), what = 2 SUM-allreduces
-// the msgcount fresh counts of this tick (and the kept entries on a loss tick).
-extern "C" int gm_shard_loopback(gm_ctx **ctxs, int32_t G, int32_t what, int32_t D) {
-  if (!ctxs || G < 2) return GM_EINVAL;
-  for (int g = 0; g < G; g++) {
-    TRY(shard_ready(ctxs[g]));
-    if (ctxs[g]->s.shard_count != G || ctxs[g]->s.shard_rank != g || ctxs[g]->n != ctxs[0]->n) return GM_EINVAL;
-    HIPCHECK(hipStreamSynchronize(ctxs[g]->stream));
+__global__ void gm_xc_mirror(int32_t *chunk, int rank, int G, size_t words) {  // stub all-gather
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < words; i += (size_t)gridDim.x * blockDim.x) {
+    const int32_t v = chunk[(size_t)rank * words + i];
+    for (int g = 0; g < G; g++)
+      if (g != rank) chunk[(size_t)g * words + i] = v;
   }
-  const size_t n = (size_t)ctxs[0]->n;
-  hipStream_t st = ctxs[0]->stream;
-  if (what == 0) {
-    const SState &s0 = ctxs[0]->s;
-    for (int g = 1; g < G; g++)
-      if (ctxs[g]->s.xlog != s0.xlog) return GM_EINVAL;
+}
+
+// The column shards' group collectives, enqueued on st. A group of one is a rank of an RCCL
+// communicator (in-place collectives) or the stub (no peers: the all-gather mirrors its slot, the
+// reductions are the identity); a group of G > 1 is a whole loopback cluster on one device: device
+// copies, and reductions into member 0 copied back to the others.
+//
+// all-gather of every shard's per-row (present, numfailed) for exchange chunk ch
+static int grp_allgather(gm_ctx **g, int G, int ch, hipStream_t st) {
+  const SState &s = g[0]->s;
+  const size_t r0 = (size_t)ch << s.xlog;
+  if (G > 1) {
+    const size_t bytes = sizeof(int32_t) * 2 * xchunk_rows(s, ch);
     for (int dst = 0; dst < G; dst++)
       for (int src = 0; src < G; src++)
-        for (int ch = 0; ch < s0.xk && src != dst; ch++) {
-          const size_t o = S_XC(s0, src, (size_t)ch << s0.xlog);
-          HIPCHECK(hipMemcpyAsync(ctxs[dst]->s.xcnt + o, ctxs[src]->s.xcnt + o, sizeof(int32_t) * 2 * xchunk_rows(s0, ch),
-                                  hipMemcpyDeviceToDevice, st));
+        if (src != dst) {
+          const size_t o = S_XC(s, src, r0);
+          HIPCHECK(hipMemcpyAsync(g[dst]->s.xcnt + o, g[src]->s.xcnt + o, bytes, hipMemcpyDeviceToDevice, st));
         }
-  } else if (what == 2) {  // msgcount: SUM of the shards' fresh counts (and kept entries on loss ticks)
-    const int t = ctxs[0]->t;
-    if (!mc_on(ctxs[0], t)) return GM_ESTATE;
-    const bool dropped = drop_tick(ctxs[0], t);
-    for (int k = 0; k < (dropped ? 2 : 1); k++) {
-      auto buf = [&](int g) { return k == 0 ? ctxs[g]->s.mc_fresh + (size_t)(t & 1) * n : ctxs[g]->s.mc_rdrop; };
-      for (int g = 1; g < G; g++) hipLaunchKernelGGL(gm_add_into, dim3(64), dim3(256), 0, st, buf(0), buf(g), n);
-      for (int g = 1; g < G; g++) HIPCHECK(hipMemcpyAsync(buf(g), buf(0), sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, st));
-    }
-  } else {
-    if (D <= 0 || D > ctxs[0]->dmax) return GM_EINVAL;
-    const size_t cnt = n * (size_t)D;
-    for (int g = 1; g < G; g++)
-      hipLaunchKernelGGL(gm_max_into, dim3(256), dim3(256), 0, st, ctxs[0]->s.status, ctxs[g]->s.status, cnt);
-    for (int g = 1; g < G; g++)
-      HIPCHECK(hipMemcpyAsync(ctxs[g]->s.status, ctxs[0]->s.status, sizeof(int32_t) * cnt, hipMemcpyDeviceToDevice, st));
+  } else if (s.stub) {  // one kernel mirrors the chunk's slot into every peer slot (the all-gather's local cost)
+    hipLaunchKernelGGL(gm_xc_mirror, dim3(256), dim3(256), 0, st, s.xcnt + S_XC(s, 0, r0), s.shard_rank,
+                       s.shard_count, (size_t)2 << s.xlog);
+    HIPCHECK(hipGetLastError());
+  } else {  // chunk-major: the chunk's slots are contiguous, rank q's at q << xlog rows -- in place
+    NCCLCHECK(ncclAllGather(s.xcnt + S_XC(s, s.shard_rank, r0), s.xcnt + S_XC(s, 0, r0), (size_t)2 << s.xlog, ncclInt32,
+                            g[0]->comm, st));
   }
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipStreamSynchronize(st));
   return GM_OK;
 }
 
-// One PIPELINED column-shard tick (tick_sharded's chunk order) of G shard contexts living on one
-// device, the collectives done by device copies / MAX kernels on one stream: per exchange chunk the
-// all-gather of the counts, every shard's round-0 draws of the chunk's rows, the MAX-reduce of their
-// statuses, every shard's acceptance; then the bounded rounds 1, 2 with their MAX-reduces. Tests
-// compare it with the fused kernel and with the phase-API loopback (gm_shard_loopback); tick_sharded
-// runs the same per-chunk steps with RCCL on the comm stream, overlapped with later chunks' merges.
-extern "C" int gm_shard_loopback_tick(gm_ctx **ctxs, int32_t G) {
+// MAX-reduce of the resolved draws: cnt words at off of status (l = 0) or of statusl[l]
+static int grp_max(gm_ctx **g, int G, int l, size_t off, size_t cnt, hipStream_t st) {
+  auto buf = [&](int i) { return (l ? g[i]->s.statusl[l] : g[i]->s.status) + off; };
+  if (G == 1) {
+    if (!g[0]->s.stub) NCCLCHECK(ncclAllReduce(buf(0), buf(0), cnt, ncclInt32, ncclMax, g[0]->comm, st));
+    return GM_OK;
+  }
+  for (int i = 1; i < G && cnt; i++) hipLaunchKernelGGL(gm_max_into, dim3(256), dim3(256), 0, st, buf(0), buf(i), cnt);
+  for (int i = 1; i < G && cnt; i++)
+    HIPCHECK(hipMemcpyAsync(buf(i), buf(0), sizeof(int32_t) * cnt, hipMemcpyDeviceToDevice, st));
+  HIPCHECK(hipGetLastError());
+  return GM_OK;
+}
+
+// msgcount: SUM-reduce of tick t's whole-row fresh counts (and of the kept entries on a loss tick)
+static int grp_mc_sum(gm_ctx **g, int G, int t, hipStream_t st) {
+  const size_t n = (size_t)g[0]->n;
+  for (int k = 0; k < (drop_tick(g[0], t) ? 2 : 1); k++) {
+    auto buf = [&](int i) { return k == 0 ? g[i]->s.mc_fresh + (size_t)(t & 1) * n : g[i]->s.mc_rdrop; };
+    if (G == 1) {
+      if (!g[0]->s.stub) NCCLCHECK(ncclAllReduce(buf(0), buf(0), n, ncclUint32, ncclSum, g[0]->comm, st));
+      continue;
+    }
+    for (int i = 1; i < G; i++) hipLaunchKernelGGL(gm_add_into, dim3(64), dim3(256), 0, st, buf(0), buf(i), n);
+    for (int i = 1; i < G; i++) HIPCHECK(hipMemcpyAsync(buf(i), buf(0), sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, st));
+  }
+  HIPCHECK(hipGetLastError());
+  return GM_OK;
+}
+
+// a loopback cluster: every shard of one SCALED cluster, in rank order, each ready to tick
+static int shard_group_ready(gm_ctx **ctxs, int G) {
   if (!ctxs || G < 2) return GM_EINVAL;
   for (int g = 0; g < G; g++) {
     TRY(shard_ready(ctxs[g]));
     const SState &sg = ctxs[g]->s;
-    if (sg.shard_count != G || sg.shard_rank != g || ctxs[g]->n != ctxs[0]->n || ctxs[g]->t != ctxs[0]->t ||
-        sg.xlog != ctxs[0]->s.xlog || sg.ramp || mc_on(ctxs[g], ctxs[g]->t))
-      return GM_EINVAL;
-    TRY(draw_settle(ctxs[g]));
-    TRY(before_tick_events(ctxs[g]));
-    HIPCHECK(hipStreamSynchronize(ctxs[g]->stream));
+    if (sg.shard_count != G || sg.shard_rank != g || ctxs[g]->n != ctxs[0]->n || sg.xlog != ctxs[0]->s.xlog) return GM_EINVAL;
   }
-  hipStream_t ls = ctxs[0]->stream;
-  const int t = ctxs[0]->t, t_send = t - 1;
-  const SState &s0 = ctxs[0]->s;
-  for (int g = 0; g < G; g++) {
-    gm_ctx *c = ctxs[g];
-    SState &s = c->s;
-    const bool drop = c->cfg.drop_pct > 0 && t_send >= c->cfg.drop_from && t_send < c->cfg.drop_to;
-    HIPCHECK(gm_launch_tick_prologue(s, t, ls, true));  // as tick_sharded: no fills
-    for (int ch = 0; ch < s.xk; ch++) {
-      const int r0 = ch << s.xlog;
-      HIPCHECK(gm_launch_band_rows(s, t, drop ? c->cfg.drop_pct : -1, r0, r0 + xchunk_rows(s, ch), ls));
-    }
-    TRY(detect_tick(c, t, ls));
+  return GM_OK;
+}
+
+// The phase API's collectives between the G shard contexts of one device (the Python
+// membership.sharded.loopback_tick drives the phases): what = 0 all-gathers xcnt, what = 1
+// MAX-allreduces status[0, n*D), what = 2 SUM-allreduces the msgcount counts of this tick.
+extern "C" int gm_shard_loopback(gm_ctx **ctxs, int32_t G, int32_t what, int32_t D) {
+  TRY(shard_group_ready(ctxs, G));
+  for (int g = 0; g < G; g++) HIPCHECK(hipStreamSynchronize(ctxs[g]->stream));
+  hipStream_t st = ctxs[0]->stream;
+  if (what == 0) {
+    for (int ch = 0; ch < ctxs[0]->s.xk; ch++) TRY(grp_allgather(ctxs, G, ch, st));
+  } else if (what == 2) {
+    if (!mc_on(ctxs[0], ctxs[0]->t)) return GM_ESTATE;
+    TRY(grp_mc_sum(ctxs, G, ctxs[0]->t, st));
+  } else {
+    if (D <= 0 || D > ctxs[0]->dmax) return GM_EINVAL;
+    TRY(grp_max(ctxs, G, 0, 0, (size_t)ctxs[0]->n * D, st));
   }
-  auto max_reduce = [&](auto buf_of, size_t off, size_t cnt) -> int {  // MAX over the shards, into every shard
-    if (!cnt) return GM_OK;
-    for (int g = 1; g < G; g++)
-      hipLaunchKernelGGL(gm_max_into, dim3(256), dim3(256), 0, ls, buf_of(0) + off, buf_of(g) + off, cnt);
-    for (int g = 1; g < G; g++)
-      HIPCHECK(hipMemcpyAsync(buf_of(g) + off, buf_of(0) + off, sizeof(int32_t) * cnt, hipMemcpyDeviceToDevice, ls));
-    return GM_OK;
-  };
-  for (int ch = 0; ch < s0.xk; ch++) {
-    const int r0 = ch << s0.xlog, r1 = r0 + xchunk_rows(s0, ch);
-    for (int g = 0; g < G; g++) HIPCHECK(gm_launch_xrows(ctxs[g]->s, r0, r1, ls));
-    for (int dst = 0; dst < G; dst++)  // the chunk's all-gather
-      for (int src = 0; src < G; src++)
-        if (src != dst) {
-          const size_t o = S_XC(s0, src, (size_t)r0);
-          HIPCHECK(hipMemcpyAsync(ctxs[dst]->s.xcnt + o, ctxs[src]->s.xcnt + o, sizeof(int32_t) * 2 * (r1 - r0),
-                                  hipMemcpyDeviceToDevice, ls));
-        }
-    for (int g = 0; g < G; g++) HIPCHECK(gm_launch_draw(ctxs[g]->s, t, 0, GM_D_FIRST, 0, ls, r0, r1));
-    TRY(max_reduce([&](int g) { return ctxs[g]->s.status; }, (size_t)r0 * GM_D_FIRST, (size_t)(r1 - r0) * GM_D_FIRST));
-    for (int g = 0; g < G; g++) HIPCHECK(gm_launch_accept(ctxs[g]->s, t, GM_D_FIRST, 0, 1, ls, r0, r1));
-  }
-  for (int l = 1; l <= 2; l++) {
-    const int D = l == 1 ? GM_D_MORE : GM_D_LAST;
-    for (int g = 0; g < G; g++) {
-      HIPCHECK(gm_launch_plist_sort(ctxs[g]->s, l, ls));
-      HIPCHECK(gm_launch_draw(ctxs[g]->s, t, l, D, l, ls));
-    }
-    TRY(max_reduce([&](int g) { return ctxs[g]->s.statusl[l]; }, 0, (size_t)s0.plist_cap[l] * D));
-    for (int g = 0; g < G; g++) HIPCHECK(gm_launch_accept(ctxs[g]->s, t, D, l, l == 1 ? 2 : -1, ls));
-  }
-  HIPCHECK(hipGetLastError());
-  // rows the bounded rounds could not take (a pending list overflowed, or a row still short after
-  // round 2): the host-driven rounds of draw_settle, each row from its own next round, with the
-  // MAX-reduce by device kernels -- every shard must count the same rows
-  for (int round = 0;; round++) {
-    std::vector<int32_t> left(G, 0);
-    for (int g = 0; g < G; g++)
-      HIPCHECK(hipMemcpyAsync(&left[g], ctxs[g]->s.npending, sizeof(int32_t), hipMemcpyDeviceToHost, ls));
-    HIPCHECK(hipStreamSynchronize(ls));
-    for (int g = 1; g < G; g++)
-      if (left[g] != left[0]) {
-        snprintf(g_errbuf, sizeof g_errbuf, "pipelined loopback tick: shards disagree on pending rows (%d vs %d)",
-                 left[g], left[0]);
-        return GM_ESTATE;
-      }
-    if (!left[0]) break;
-    if (round >= GM_MAX_ROUNDS) return GM_ERANGE;
-    for (int g = 0; g < G; g++) HIPCHECK(gm_launch_draw(ctxs[g]->s, t, 1, GM_D_MORE, 0, ls));
-    TRY(max_reduce([&](int g) { return ctxs[g]->s.status; }, 0, (size_t)ctxs[0]->n * GM_D_MORE));
-    for (int g = 0; g < G; g++) {
-      HIPCHECK(hipMemsetAsync(ctxs[g]->s.npending, 0, sizeof(int32_t), ls));
-      HIPCHECK(gm_launch_accept(ctxs[g]->s, t, GM_D_MORE, 0, 0, ls));
-    }
-  }
-  for (int g = 0; g < G; g++) TRY(gm_shard_end_tick(ctxs[g]));
+  HIPCHECK(hipStreamSynchronize(st));
   return GM_OK;
 }
 
@@ -2442,52 +2408,28 @@ extern "C" int gm_shard_stub(gm_ctx *c, int32_t on) {
   return GM_OK;
 }
 
-__global__ void gm_xc_mirror(int32_t *chunk, int rank, int G, size_t words) {  // stub all-gather
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < words; i += (size_t)gridDim.x * blockDim.x) {
-    const int32_t v = chunk[(size_t)rank * words + i];
-    for (int g = 0; g < G; g++)
-      if (g != rank) chunk[(size_t)g * words + i] = v;
-  }
-}
-
-// the all-gather of this shard's per-row (present, numfailed) for exchange chunk ch (stub: mirrored
-// into every peer slot), on stream st
-static int xcnt_allgather(gm_ctx *c, int ch, hipStream_t st) {
-  SState &s = c->s;
-  const size_t R = (size_t)1 << s.xlog, r0 = (size_t)ch << s.xlog;
-  int32_t *own = s.xcnt + S_XC(s, s.shard_rank, r0);
-  if (s.stub) {  // one kernel mirrors the chunk's slot into every peer slot (the all-gather's local cost)
-    hipLaunchKernelGGL(gm_xc_mirror, dim3(256), dim3(256), 0, st, s.xcnt + S_XC(s, 0, r0), s.shard_rank,
-                       s.shard_count, (size_t)2 << s.xlog);
-    HIPCHECK(hipGetLastError());
-    return GM_OK;
-  }
-  // chunk-major: the chunk's G slots are contiguous, rank g's at g * R rows -- in place
-  NCCLCHECK(ncclAllGather(own, s.xcnt + S_XC(s, 0, r0), R * 2, ncclInt32, c->comm, st));
-  return GM_OK;
-}
-
 // Bounded rounds 1 and 2 of tick t over the rows round 0 left pending: their sorted list (identical on
 // every rank) takes the next 64 S2 outputs, then up to 256 rows the next 256; a row still short sets
 // GM_ERR_DRAWS. Rows the rounds could not take are counted in npending (draw_settle finishes them with
 // host-driven rounds).
-static int run_bounded(gm_ctx *c, int t) {
-  SState &s = c->s;
+static int run_bounded(gm_ctx **g, int G, int t) {
+  hipStream_t st = g[0]->stream;
   for (int l = 1; l <= 2; l++) {
     const int D = l == 1 ? GM_D_MORE : GM_D_LAST;
-    HIPCHECK(gm_launch_plist_sort(s, l, c->stream));
-    HIPCHECK(gm_launch_draw(s, t, l, D, l, c->stream));
-    if (!s.stub)
-      NCCLCHECK(ncclAllReduce(s.statusl[l], s.statusl[l], (size_t)s.plist_cap[l] * D, ncclInt32, ncclMax, c->comm,
-                              c->stream));
-    HIPCHECK(gm_launch_accept(s, t, D, l, l == 1 ? 2 : -1, c->stream));
+    for (int i = 0; i < G; i++) {
+      HIPCHECK(gm_launch_plist_sort(g[i]->s, l, st));
+      HIPCHECK(gm_launch_draw(g[i]->s, t, l, D, l, st));
+    }
+    TRY(grp_max(g, G, l, 0, (size_t)g[0]->s.plist_cap[l] * D, st));
+    for (int i = 0; i < G; i++) HIPCHECK(gm_launch_accept(g[i]->s, t, D, l, l == 1 ? 2 : -1, st));
   }
-  if (getenv("GM_DEBUG_ROUNDS")) {  // diagnostics: rows left after round 0, error flags
+  for (int i = 0; i < G && getenv("GM_DEBUG_ROUNDS"); i++) {  // diagnostics: rows left after round 0, error flags
+    const SState &s = g[i]->s;
     uint32_t pc1 = 0, pc2 = 0, e = 0;
-    HIPCHECK(hipMemcpyAsync(&pc1, s.plist_cnt[1], sizeof pc1, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(hipMemcpyAsync(&pc2, s.plist_cnt[2], sizeof pc2, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(hipMemcpyAsync(&e, s.err, sizeof e, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    HIPCHECK(hipMemcpyAsync(&pc1, s.plist_cnt[1], sizeof pc1, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(&pc2, s.plist_cnt[2], sizeof pc2, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(&e, s.err, sizeof e, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
     fprintf(stderr, "[gm] t=%d rows pending after round 0: %u (cap %d), after round 1: %u (cap %d), err 0x%x\n", t,
             pc1, s.plist_cap[1], pc2, s.plist_cap[2], e);
   }
@@ -2502,18 +2444,61 @@ static int run_bounded(gm_ctx *c, int t) {
 // the ranks' RCCL calls stay in step.
 // ds: the stream whose work decides the counts (the pipelined tick's comm stream: the copy follows
 // its last acceptance directly instead of behind a cross-stream join)
-static int end_draws(gm_ctx *c, bool deferred, hipStream_t ds = nullptr) {
-  SState &s = c->s;
-  if (!deferred) TRY(run_bounded(c, c->t));
-  if (!ds) ds = c->stream;
-  HIPCHECK(hipMemcpyAsync(c->draw_left_h, s.npending, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ds));
-  HIPCHECK(hipEventRecord(c->draw_ev, ds));
-  c->draw_rounds = deferred;
-  c->t--;  // gm_tick advances globaltime
-  c->draw_check = true;  // before end_tick: the msgcount phase waits for draw_settle
-  TRY(gm_shard_end_tick(c));
-  c->ticks_done--;  // gm_tick counts it
+static int end_draws(gm_ctx **g, int G, bool deferred, hipStream_t ds) {
+  if (!deferred) TRY(run_bounded(g, G, g[0]->t));
+  for (int i = 0; i < G; i++)
+    HIPCHECK(hipMemcpyAsync(g[i]->draw_left_h, g[i]->s.npending, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ds));
+  HIPCHECK(hipEventRecord(g[0]->draw_ev, ds));
+  for (int i = 0; i < G; i++) {
+    g[i]->draw_rounds = deferred;
+    g[i]->draw_check = true;  // before shard_finish: the msgcount phase waits for draw_settle
+    TRY(shard_finish(g[i], g[0]->stream));
+  }
   return GM_OK;
+}
+
+// Every member counts the same pending rows (each replays every row's draws and accepts the same
+// MAX-reduced statuses): anything else is a bug caught here
+static int pending_agree(gm_ctx **g, int G) {
+  for (int i = 1; i < G; i++)
+    for (int k = 0; k < 2; k++)
+      if (g[i]->draw_left_h[k] != g[0]->draw_left_h[k]) {
+        snprintf(g_errbuf, sizeof g_errbuf, "pipelined loopback tick: shards disagree on pending rows (%d vs %d)",
+                 g[i]->draw_left_h[k], g[0]->draw_left_h[k]);
+        return GM_ESTATE;
+      }
+  return GM_OK;
+}
+// the rows still drawing after the rounds enqueued so far, read back with a wait
+static int read_pending(gm_ctx **g, int G, int32_t *pend) {
+  for (int i = 0; i < G; i++)
+    HIPCHECK(hipMemcpyAsync(g[i]->draw_left_h, g[i]->s.npending, sizeof(int32_t), hipMemcpyDeviceToHost, g[0]->stream));
+  HIPCHECK(hipStreamSynchronize(g[0]->stream));
+  *pend = g[0]->draw_left_h[0];
+  return pending_agree(g, G);
+}
+
+// One host-driven round of tick t: every row still drawing takes D more S2 outputs (round >= 1: each
+// row from its own next round, gm_s_draw reads it from pending[r]); *pend: the rows left after it
+static int draw_round(gm_ctx **g, int G, int t, int round, int D, int32_t *pend) {
+  hipStream_t st = g[0]->stream;
+  for (int i = 0; i < G; i++) HIPCHECK(gm_launch_draw(g[i]->s, t, round, D, 0, st));
+  TRY(grp_max(g, G, 0, 0, (size_t)g[0]->n * D, st));
+  for (int i = 0; i < G; i++) {
+    HIPCHECK(hipMemsetAsync(g[i]->s.npending, 0, sizeof(int32_t), st));
+    HIPCHECK(gm_launch_accept(g[i]->s, t, D, 0, 0, st));
+  }
+  return read_pending(g, G, pend);
+}
+
+static int draws_exhausted(gm_ctx **g, int G) {  // a row that never finds its targets: same guard as gm_s_pick
+  const uint32_t e = GM_ERR_DRAWS;
+  for (int i = 0; i < G; i++) {
+    HIPCHECK(hipMemcpyAsync(g[i]->s.err, &e, sizeof e, hipMemcpyHostToDevice, g[0]->stream));
+    g[i]->latched = GM_ERANGE;
+  }
+  HIPCHECK(hipStreamSynchronize(g[0]->stream));
+  return GM_ERANGE;
 }
 
 // The column-shard tick, pipelined over the exchange's row chunks (north_star: the exchange
@@ -2524,142 +2509,137 @@ static int end_draws(gm_ctx *c, bool deferred, hipStream_t ds = nullptr) {
 // the acceptance -- while the band kernels of chunks ch+1.. still run. A row's draws need only
 // its own post-sweep row (in chunk ch) and the other ranks' counts of that row; the acceptance
 // appends to the inboxes of tick t+1 (the other parity), which no band kernel of tick t reads.
-// Then the bounded rounds 1, 2 on the compute stream. Ticks that record msgcount (their
+// The bounded rounds 1, 2 are left to draw_settle. Ticks that record msgcount (their
 // fresh-count all-reduce precedes every draw), the join ramp and the host-driven draw loop (mass
 // failure, heavy loss) take the same steps unchunked.
-static int tick_sharded(gm_ctx *c) {
-  if (!c->comm && !c->s.stub) return GM_EUNSUPPORTED;  // multi-GPU ticks need gm_comm_init (or the phase API + loopback)
-  SState &s = c->s;
-  const size_t n = (size_t)c->n;
-  const int64_t nfailed = c->nfailed;
+// A loopback group shares its first member's stream pair: G concurrent pairs on one device starve
+// each other's small kernels (on a node every shard has its GPU to itself).
+static int tick_sharded(gm_ctx **g, int G) {
+  gm_ctx *L = g[0];
+  if (G == 1 && !L->comm && !L->s.stub) return GM_EUNSUPPORTED;  // multi-GPU ticks need gm_comm_init (or a loopback)
+  const SState &s0 = L->s;  // the chunking is the same on every member
+  const size_t n = (size_t)L->n;
+  const int t = L->t;
+  hipStream_t st = L->stream, cs = L->p_comm;
   // mass failure or heavy loss leaves many entries stale, so rows need many draws: the
   // host-driven unbounded loop below (also GM_SHARD_SYNC=1)
-  const bool sync = c->shard_sync == 1 || (c->shard_sync < 0 && (c->cfg.drop_pct >= 30 || 10 * nfailed > (int64_t)n));
-  const bool pipe = !sync && !mc_on(c, c->t) && !s.ramp && !(getenv("GM_SHARD_PIPE") && !atoi(getenv("GM_SHARD_PIPE")));
+  const bool sync = L->shard_sync == 1 || (L->shard_sync < 0 && (L->cfg.drop_pct >= 30 || 10 * L->nfailed > (int64_t)n));
+  const bool pipe = !sync && !mc_on(L, t) && !s0.ramp && !(getenv("GM_SHARD_PIPE") && !atoi(getenv("GM_SHARD_PIPE")));
   if (pipe) {
-    TRY(shard_ready(c));
-    TRY(before_tick_events(c));
-    const int t = c->t, t_send = t - 1;
-    const bool drop = c->cfg.drop_pct > 0 && t_send >= c->cfg.drop_from && t_send < c->cfg.drop_to;
     // no fills: gm_s_xrows writes this rank's xcnt slots whole (no join ramp here) and gm_s_mtgen
     // zeroes the draw rounds' counters
-    HIPCHECK(gm_launch_tick_prologue(s, t, c->stream, true));
-    hipEvent_t k0 = nullptr, k1 = nullptr;
-    if (c->timing) TRY(timing_slot(c, &k0, &k1));
-    if (k0) HIPCHECK(hipEventRecord(k0, c->stream));
-    for (int ch = 0; ch < s.xk; ch++) {
-      const int r0 = ch << s.xlog;
-      HIPCHECK(gm_launch_band_rows(s, t, drop ? c->cfg.drop_pct : -1, r0, r0 + xchunk_rows(s, ch), c->stream));
-      const int zr = c->diag_zero_row;
-      if (zr >= r0 && zr < r0 + xchunk_rows(s, ch) && zr < c->n)
-        for (int b = 0; b < s.nb; b++)
-          HIPCHECK(hipMemsetAsync(s.table + ((size_t)b * n + zr) * s.band, 0, s.band, c->stream));
-      HIPCHECK(hipEventRecord(c->p_chev[ch], c->stream));
+    for (int i = 0; i < G; i++) HIPCHECK(gm_launch_tick_prologue(g[i]->s, t, st, true));
+    hipEvent_t k0 = nullptr, k1 = nullptr;  // the first member's: they bracket the group's band kernels
+    if (L->timing) TRY(timing_slot(L, &k0, &k1, st));
+    if (k0) HIPCHECK(hipEventRecord(k0, st));
+    for (int ch = 0; ch < s0.xk; ch++) {
+      const int r0 = ch << s0.xlog, r1 = r0 + xchunk_rows(s0, ch);
+      for (int i = 0; i < G; i++) {
+        const SState &s = g[i]->s;
+        HIPCHECK(gm_launch_band_rows(s, t, drop_tick(g[i], t) ? g[i]->cfg.drop_pct : -1, r0, r1, st));
+        const int zr = g[i]->diag_zero_row;
+        if (zr >= r0 && zr < r1)
+          for (int b = 0; b < s.nb; b++) HIPCHECK(hipMemsetAsync(s.table + ((size_t)b * n + zr) * s.band, 0, s.band, st));
+      }
+      HIPCHECK(hipEventRecord(L->p_chev[ch], st));
     }
-    if (k1) HIPCHECK(hipEventRecord(k1, c->stream));
-    TRY(detect_tick(c, t, c->stream));  // on the compute stream, beside the comm stream's draws
-    hipStream_t cs = c->p_comm;
-    for (int ch = 0; ch < s.xk; ch++) {
-      const int r0 = ch << s.xlog, r1 = r0 + xchunk_rows(s, ch);
-      HIPCHECK(hipStreamWaitEvent(cs, c->p_chev[ch], 0));
-      HIPCHECK(gm_launch_xrows(s, r0, r1, cs));
-      TRY(xcnt_allgather(c, ch, cs));
-      HIPCHECK(gm_launch_draw(s, t, 0, GM_D_FIRST, 0, cs, r0, r1));
-      if (!s.stub)
-        NCCLCHECK(ncclAllReduce(s.status + (size_t)r0 * GM_D_FIRST, s.status + (size_t)r0 * GM_D_FIRST,
-                                (size_t)(r1 - r0) * GM_D_FIRST, ncclInt32, ncclMax, c->comm, cs));
-      HIPCHECK(gm_launch_accept(s, t, GM_D_FIRST, 0, 1, cs, r0, r1));
+    if (k1) HIPCHECK(hipEventRecord(k1, st));
+    for (int i = 0; i < G; i++) TRY(detect_tick(g[i], t, st));  // on the compute stream, beside the comm stream's draws
+    for (int ch = 0; ch < s0.xk; ch++) {
+      const int r0 = ch << s0.xlog, r1 = r0 + xchunk_rows(s0, ch);
+      HIPCHECK(hipStreamWaitEvent(cs, L->p_chev[ch], 0));
+      for (int i = 0; i < G; i++) HIPCHECK(gm_launch_xrows(g[i]->s, r0, r1, cs));
+      TRY(grp_allgather(g, G, ch, cs));
+      for (int i = 0; i < G; i++) HIPCHECK(gm_launch_draw(g[i]->s, t, 0, GM_D_FIRST, 0, cs, r0, r1));
+      TRY(grp_max(g, G, 0, (size_t)r0 * GM_D_FIRST, (size_t)(r1 - r0) * GM_D_FIRST, cs));
+      for (int i = 0; i < G; i++) HIPCHECK(gm_launch_accept(g[i]->s, t, GM_D_FIRST, 0, 1, cs, r0, r1));
     }
-    HIPCHECK(hipEventRecord(c->p_done, cs));
-    HIPCHECK(hipStreamWaitEvent(c->stream, c->p_done, 0));
-    return end_draws(c, true, cs);
+    HIPCHECK(hipEventRecord(L->p_done, cs));
+    HIPCHECK(hipStreamWaitEvent(st, L->p_done, 0));
+    return end_draws(g, G, true, cs);
   }
-  TRY(gm_shard_merge(c));
-  for (int ch = 0; ch < s.xk; ch++) TRY(xcnt_allgather(c, ch, c->stream));
-  if (!s.stub && mc_on(c, c->t)) {  // msgcount: whole-row fresh counts (and kept entries on loss ticks)
-    NCCLCHECK(ncclAllReduce(s.mc_fresh + (size_t)(c->t & 1) * n, s.mc_fresh + (size_t)(c->t & 1) * n, n, ncclUint32,
-                            ncclSum, c->comm, c->stream));
-    if (drop_tick(c, c->t))
-      NCCLCHECK(ncclAllReduce(s.mc_rdrop, s.mc_rdrop, n, ncclUint32, ncclSum, c->comm, c->stream));
-  }
+  for (int i = 0; i < G; i++) TRY(shard_merge(g[i], st));
+  for (int ch = 0; ch < s0.xk; ch++) TRY(grp_allgather(g, G, ch, st));
+  if (mc_on(L, t)) TRY(grp_mc_sum(g, G, t, st));
   if (!sync) {
     // bounded rounds, stream-ordered (no host round trip): round 0 = every row's first 16
     // S2 outputs; rows left pending go to a list (sorted: identical on every rank) that
     // round 1 serves with the next 64; a row still short after that sets GM_ERR_DRAWS
-    for (int l = 1; l <= 2; l++) HIPCHECK(hipMemsetAsync(s.plist_cnt[l], 0, sizeof(uint32_t), c->stream));
-    HIPCHECK(hipMemsetAsync(s.npending, 0, sizeof(int32_t), c->stream));
-    HIPCHECK(gm_launch_draw(s, c->t, 0, GM_D_FIRST, 0, c->stream));
-    if (!s.stub)
-      NCCLCHECK(ncclAllReduce(s.status, s.status, n * GM_D_FIRST, ncclInt32, ncclMax, c->comm, c->stream));
-    HIPCHECK(gm_launch_accept(s, c->t, GM_D_FIRST, 0, 1, c->stream));
-    return end_draws(c, false);
-  }
-  int round = 0, D = GM_D_FIRST;
-  for (;;) {
-    TRY(gm_shard_draw(c, round, D));
-    if (!s.stub)
-      NCCLCHECK(ncclAllReduce(s.status, s.status, n * D, ncclInt32, ncclMax, c->comm, c->stream));
-    int32_t pend = 0;
-    TRY(gm_shard_accept(c, D, &pend));
-    if (getenv("GM_DEBUG_ROUNDS")) fprintf(stderr, "[gm] t=%d round %d: %d rows still drawing\n", c->t, round, pend);
-    if (pend == 0) break;
-    if (++round > GM_MAX_ROUNDS) {  // a row that never finds its targets: same guard as gm_s_pick
-      uint32_t e = GM_ERR_DRAWS;
-      HIPCHECK(ctx_memcpy(c, s.err, &e, sizeof e, hipMemcpyHostToDevice));
-      c->latched = GM_ERANGE;
-      return c->latched;
+    for (int i = 0; i < G; i++) {
+      const SState &s = g[i]->s;
+      for (int l = 1; l <= 2; l++) HIPCHECK(hipMemsetAsync(s.plist_cnt[l], 0, sizeof(uint32_t), st));
+      HIPCHECK(hipMemsetAsync(s.npending, 0, sizeof(int32_t), st));
+      HIPCHECK(gm_launch_draw(s, t, 0, GM_D_FIRST, 0, st));
     }
-    D = GM_D_MORE;
+    TRY(grp_max(g, G, 0, 0, n * GM_D_FIRST, st));
+    for (int i = 0; i < G; i++) HIPCHECK(gm_launch_accept(g[i]->s, t, GM_D_FIRST, 0, 1, st));
+    return end_draws(g, G, false, st);
   }
-  c->t--;  // gm_tick advances globaltime
-  TRY(gm_shard_end_tick(c));
-  c->ticks_done--;  // gm_tick counts it
+  int32_t pend = 0;
+  for (int round = 0;; round++) {
+    TRY(draw_round(g, G, t, round, round ? GM_D_MORE : GM_D_FIRST, &pend));
+    if (getenv("GM_DEBUG_ROUNDS")) fprintf(stderr, "[gm] t=%d round %d: %d rows still drawing\n", t, round, pend);
+    if (pend == 0) break;
+    if (round >= GM_MAX_ROUNDS) return draws_exhausted(g, G);
+  }
+  for (int i = 0; i < G; i++) TRY(shard_finish(g[i], st));
   return GM_OK;
 }
 
 // The rows the last sharded tick's bounded rounds left (a full pending list, or still short of
-// targets after 336 S2 outputs): host-driven rounds, each row continuing from its own next round
-// (gm_s_draw with round >= 1 reads it from pending[r]), until every row has its targets --
-// tick t = c->t - 1 completes before anything reads it or the next tick starts.
-static int draw_settle(gm_ctx *c) {
-  if (!c->draw_check) return c->latched;
-  c->draw_check = false;
+// targets after 336 S2 outputs): host-driven rounds, each row continuing from its own next round,
+// until every row has its targets -- tick t = c->t - 1 completes before anything reads it or the
+// next tick starts.
+static int draw_settle(gm_ctx **g, int G) {
+  gm_ctx *L = g[0];
+  if (!L->draw_check) return L->latched;
+  const bool deferred = L->draw_rounds;
+  for (int i = 0; i < G; i++) g[i]->draw_check = g[i]->draw_rounds = false;
   // the next tick's launches wait on these two counts: spin on the event rather than block (the
   // wait costs 2-18 us of GPU idle per pipelined tick, profiles/r06/stub_tail/). No work of the
   // next tick is enqueued before it: its S2 precompute zeroes the counts the copy reads
   hipError_t q;
-  while ((q = hipEventQuery(c->draw_ev)) == hipErrorNotReady) {
+  while ((q = hipEventQuery(L->draw_ev)) == hipErrorNotReady) {
   }
   HIPCHECK(q);
-  int32_t pend = c->draw_left_h[0];
-  const int t = c->t - 1;
-  const size_t n = (size_t)c->n;
-  if (c->draw_rounds) {  // the pipelined tick's bounded rounds, only if round 0 left rows pending
-    c->draw_rounds = false;
-    if (c->draw_left_h[1] > 0) {
-      TRY(run_bounded(c, t));
-      HIPCHECK(hipMemcpyAsync(&pend, c->s.npending, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-      HIPCHECK(hipStreamSynchronize(c->stream));
-    }
+  TRY(pending_agree(g, G));
+  int32_t pend = L->draw_left_h[0];
+  const int t = L->t - 1;
+  if (deferred && L->draw_left_h[1] > 0) {  // the pipelined tick's bounded rounds, only if round 0 left rows pending
+    TRY(run_bounded(g, G, t));
+    TRY(read_pending(g, G, &pend));
   }
   for (int round = 0; pend > 0; round++) {
     if (getenv("GM_DEBUG_ROUNDS")) fprintf(stderr, "[gm] t=%d settle round %d: %d rows still drawing\n", t, round, pend);
-    if (round >= GM_MAX_ROUNDS) {
-      uint32_t e = GM_ERR_DRAWS;
-      HIPCHECK(ctx_memcpy(c, c->s.err, &e, sizeof e, hipMemcpyHostToDevice));
-      c->latched = GM_ERANGE;
-      return c->latched;
-    }
-    HIPCHECK(gm_launch_draw(c->s, t, 1, GM_D_MORE, 0, c->stream));
-    if (!c->s.stub)
-      NCCLCHECK(ncclAllReduce(c->s.status, c->s.status, n * GM_D_MORE, ncclInt32, ncclMax, c->comm, c->stream));
-    HIPCHECK(hipMemsetAsync(c->s.npending, 0, sizeof(int32_t), c->stream));
-    HIPCHECK(gm_launch_accept(c->s, t, GM_D_MORE, 0, 0, c->stream));
-    HIPCHECK(hipMemcpyAsync(&pend, c->s.npending, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    if (round >= GM_MAX_ROUNDS) return draws_exhausted(g, G);
+    TRY(draw_round(g, G, t, 1, GM_D_MORE, &pend));
   }
-  if (mc_on(c, t)) HIPCHECK(gm_launch_msgcount(c->s, t, drop_tick(c, t), 1, c->stream));
-  return c->latched;
+  for (int i = 0; i < G; i++)
+    if (mc_on(g[i], t)) HIPCHECK(gm_launch_msgcount(g[i]->s, t, drop_tick(g[i], t), 1, L->stream));
+  return L->latched;
+}
+
+// One column-shard tick of the G shard contexts of one cluster living on one device (tests,
+// scripts/sb_loopback_profile.py): the tick gm_tick runs per rank (tick_sharded, draw_settle),
+// with the group's collectives done by device copies and reduce kernels instead of RCCL. The
+// join ramp and msgcount recording are not driven here (GM_EINVAL).
+extern "C" int gm_shard_loopback_tick(gm_ctx **ctxs, int32_t G) {
+  TRY(shard_group_ready(ctxs, G));
+  for (int g = 0; g < G; g++)
+    if (ctxs[g]->t != ctxs[0]->t || ctxs[g]->s.ramp || mc_on(ctxs[g], ctxs[g]->t)) return GM_EINVAL;
+  TRY(draw_settle(ctxs, G));
+  for (int g = 0; g < G; g++) {
+    TRY(before_tick_events(ctxs[g]));
+    HIPCHECK(hipStreamSynchronize(ctxs[g]->stream));  // the tick runs on the first member's streams
+  }
+  int rc = tick_sharded(ctxs, G);
+  for (int g = 0; g < G && rc == GM_OK; g++) advance(ctxs[g]);
+  // settled here, not lazily as gm_tick does: a later call on one member alone (gm_sync, gm_read_*,
+  // gm_drain_events) could not reduce across its peers
+  if (rc == GM_OK) rc = draw_settle(ctxs, G);
+  HIPCHECK(hipStreamSynchronize(ctxs[0]->p_comm));
+  HIPCHECK(hipStreamSynchronize(ctxs[0]->stream));
+  return rc;
 }
 
 // ------------------------------------------------------------ PARTIAL row shards
@@ -2748,95 +2728,101 @@ static int partial_caps(gm_ctx *c) {
   return GM_OK;
 }
 
-static int partial_exchange_chunk(gm_ctx *c, int ch, int64_t *roff) {
-  PState &p = c->p;
-  const int G = p.G, V = p.V;
-  hipStream_t cs = c->p_comm;
-  const XChunk x = xchunk(c, ch);
-  std::vector<size_t> hs(G), hsd(G), hr(G), hrd(G), ls(G), lsd(G), lr(G), lrd(G);
-  for (int q = 0; q < G; q++) {
-    hs[q] = x.sc[q] * 8;
-    hsd[q] = x.sd[q] * 8;
-    hr[q] = x.rc[q] * 8;
-    hrd[q] = x.rd[q] * 8;
-    ls[q] = x.sc[q] * V;
-    lsd[q] = x.sd[q] * V;
-    lr[q] = x.rc[q] * V;
-    lrd[q] = x.rd[q] * V;
+// The block capacities (send counts of a rank, receive counts of its peers) derive from the crash
+// set each rank was given (gm_set_failed): a rank holding another set would size its ncclAllToAllv
+// differently and hang or corrupt it. After each change the group agrees on the set's hash -- an RCCL
+// rank by one MAX-allreduce of (h, ~h), a loopback group on the host -- and any disagreement latches
+// GM_ESTATE on every member.
+static int px_agree(gm_ctx **g, int G, hipStream_t st) {
+  bool same = true;
+  if (G == 1) {
+    gm_ctx *c = g[0];
+    if (!c->p_crash_dev) {
+      HIPCHECK(hipMalloc(&c->p_crash_dev, 2 * sizeof(uint64_t)));
+      c->allocs.push_back(c->p_crash_dev);
+    }
+    uint64_t hv[2] = {c->p_crash_hash, ~c->p_crash_hash}, mx[2] = {0, 0};
+    HIPCHECK(hipMemcpyAsync(c->p_crash_dev, hv, sizeof hv, hipMemcpyHostToDevice, st));
+    NCCLCHECK(ncclAllReduce(c->p_crash_dev, c->p_crash_dev, 2, ncclUint64, ncclMax, c->comm, st));
+    HIPCHECK(hipMemcpyAsync(mx, c->p_crash_dev, sizeof mx, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    same = mx[0] == hv[0] && mx[1] == hv[1];
   }
-  if (x.rbase + x.rrows > (size_t)(p.n - p.nloc)) return GM_ESTATE;
-  if (ch == 0) HIPCHECK(hipMemsetAsync(p.pk_cnt, 0, sizeof(int32_t) * p.nchunk * G, cs));
-  HIPCHECK(gm_launch_partial_pack(p, c->t, ch, cs));
-  NCCLCHECK(ncclAllToAllv(p.pk_hdr, hs.data(), hsd.data(), p.recv_hdr, hr.data(), hrd.data(), ncclInt32, c->comm, cs));
-  NCCLCHECK(ncclAllToAllv(p.pk_list, ls.data(), lsd.data(), p.recv_list[c->t & 1], lr.data(), lrd.data(), ncclUint32,
-                          c->comm, cs));
-  HIPCHECK(gm_launch_partial_unpack(p, c->t, (int)x.rbase, (int)x.rrows, cs));
-  *roff = (int64_t)(x.rbase + x.rrows);
+  for (int i = 1; i < G; i++) same &= g[i]->p_crash_hash == g[0]->p_crash_hash;
+  for (int i = 0; i < G && !same; i++) g[i]->latched = GM_ESTATE;
+  return same ? GM_OK : GM_ESTATE;
+}
+
+// The exchange of chunk ch on the comm stream: every member packs, then each member receives its
+// blocks -- two ncclAllToAllv for an RCCL rank, device copies from its peers' packed blocks in a
+// loopback group (same layout; both sides must have sized the block alike) -- and unpacks them.
+static int px_exchange(gm_ctx **g, int G, int ch, hipStream_t cs) {
+  const int t = g[0]->t, V = g[0]->p.V;
+  for (int i = 0; i < G; i++) {
+    const PState &p = g[i]->p;
+    if (ch == 0) HIPCHECK(hipMemsetAsync(p.pk_cnt, 0, sizeof(int32_t) * p.nchunk * p.G, cs));
+    HIPCHECK(gm_launch_partial_pack(p, t, ch, cs));
+  }
+  for (int i = 0; i < G; i++) {
+    gm_ctx *c = g[i];
+    const PState &p = c->p;
+    const XChunk x = xchunk(c, ch);
+    if (x.rbase + x.rrows > (size_t)(p.n - p.nloc)) return GM_ESTATE;
+    if (G == 1) {
+      const int W = p.G;
+      std::vector<size_t> hs(W), hsd(W), hr(W), hrd(W), ls(W), lsd(W), lr(W), lrd(W);
+      for (int q = 0; q < W; q++) {
+        hs[q] = x.sc[q] * 8;
+        hsd[q] = x.sd[q] * 8;
+        hr[q] = x.rc[q] * 8;
+        hrd[q] = x.rd[q] * 8;
+        ls[q] = x.sc[q] * V;
+        lsd[q] = x.sd[q] * V;
+        lr[q] = x.rc[q] * V;
+        lrd[q] = x.rd[q] * V;
+      }
+      NCCLCHECK(ncclAllToAllv(p.pk_hdr, hs.data(), hsd.data(), p.recv_hdr, hr.data(), hrd.data(), ncclInt32, c->comm, cs));
+      NCCLCHECK(ncclAllToAllv(p.pk_list, ls.data(), lsd.data(), p.recv_list[t & 1], lr.data(), lrd.data(), ncclUint32,
+                              c->comm, cs));
+    }
+    for (int j = 0; j < G; j++) {
+      if (j == i || !x.rc[j]) continue;
+      const XChunk xj = xchunk(g[j], ch);
+      const PState &pj = g[j]->p;
+      if (xj.sc[i] != x.rc[j]) return GM_ESTATE;
+      HIPCHECK(hipMemcpyAsync(p.recv_hdr + x.rd[j] * 8, pj.pk_hdr + xj.sd[i] * 8, sizeof(int32_t) * 8 * x.rc[j],
+                              hipMemcpyDeviceToDevice, cs));
+      HIPCHECK(hipMemcpyAsync(p.recv_list[t & 1] + x.rd[j] * V, pj.pk_list + xj.sd[i] * V, sizeof(uint32_t) * V * x.rc[j],
+                              hipMemcpyDeviceToDevice, cs));
+    }
+    HIPCHECK(gm_launch_partial_unpack(p, t, (int)x.rbase, (int)x.rrows, cs));
+    c->p_recv_last = (int64_t)(x.rbase + x.rrows);  // the last chunk's: every list received this tick
+  }
   return GM_OK;
 }
 
-// One PARTIAL tick of G row-shard contexts living on one device (tests): the local
-// kernels of every shard, the exchange partial_exchange_chunk does by device copies (same layout),
-// the unpack, and the globaltime advance gm_tick does.
+// One PARTIAL tick of the G row-shard contexts of one cluster living on one device (tests,
+// scripts/partial_shard_profile.py): the tick gm_tick runs per rank (tick_partial), the exchange by
+// device copies instead of RCCL. A device error of the tick (an overflowing block: GM_ERANGE) is
+// returned by this call.
 extern "C" int gm_partial_loopback_tick(gm_ctx **ctxs, int32_t G) {
   if (!ctxs || G < 2) return GM_EINVAL;
   for (int g = 0; g < G; g++) {
     gm_ctx *c = ctxs[g];
     if (!c || c->cfg.mode != GM_MODE_PARTIAL || c->p.G != G || c->p.rank != g || c->t != ctxs[0]->t ||
-        c->n != ctxs[0]->n || c->p.V != ctxs[0]->p.V)
+        c->n != ctxs[0]->n || c->p.V != ctxs[0]->p.V || c->p.nchunk != ctxs[0]->p.nchunk)
       return GM_EINVAL;
     if (c->latched != GM_OK) return c->latched;
   }
   for (int g = 0; g < G; g++) TRY(before_tick_events(ctxs[g]));
-  // every shard's kernels on ONE stream, shard after shard: the sum of the shards' own costs (8
-  // concurrent streams on one device starve each other's small worklist kernels; on a node every
-  // shard has its GPU to itself)
-  for (int g = 0; g < G; g++) HIPCHECK(hipStreamSynchronize(ctxs[g]->stream));
-  hipStream_t ls = ctxs[0]->stream;
-  for (int g = 0; g < G; g++) {
-    gm_ctx *c = ctxs[g];
-    const int t_send = c->t - 1;
-    const bool drop = c->cfg.drop_pct > 0 && t_send >= c->cfg.drop_from && t_send < c->cfg.drop_to;
-    PState st = c->p;
-    st.drop_pct = drop ? c->cfg.drop_pct : -1;
-    HIPCHECK(gm_launch_partial_tick(st, c->t, c->p_mtraw, ls, nullptr, nullptr));
-  }
-  const int K = ctxs[0]->p.nchunk;
-  for (int g = 0; g < G; g++)
-    if (ctxs[g]->p.nchunk != K) return GM_EINVAL;
-  // the blocks partial_exchange_chunk's all-to-allv moves, by device copies
-  const int V = ctxs[0]->p.V;
-  std::vector<size_t> roff(G, 0);
-  for (int g = 0; g < G; g++) {  // every shard packs its records into its outgoing blocks (as on the comm stream)
-    PState &pg = ctxs[g]->p;
-    HIPCHECK(hipMemsetAsync(pg.pk_cnt, 0, sizeof(int32_t) * K * G, ls));
-    for (int ch = 0; ch < K; ch++) HIPCHECK(gm_launch_partial_pack(pg, ctxs[g]->t, ch, ls));
-  }
-  for (int ch = 0; ch < K; ch++)
-    for (int q = 0; q < G; q++) {
-      PState &dq = ctxs[q]->p;
-      hipStream_t st = ls;
-      const XChunk xq = xchunk(ctxs[q], ch);
-      for (int g = 0; g < G; g++) {
-        if (g == q || !xq.rc[g]) continue;
-        const XChunk xg = xchunk(ctxs[g], ch);
-        const PState &sg = ctxs[g]->p;
-        if (xg.sc[q] != xq.rc[g]) return GM_ESTATE;
-        HIPCHECK(hipMemcpyAsync(dq.recv_hdr + xq.rd[g] * 8, sg.pk_hdr + xg.sd[q] * 8, sizeof(int32_t) * 8 * xq.rc[g],
-                                hipMemcpyDeviceToDevice, st));
-        HIPCHECK(hipMemcpyAsync(dq.recv_list[ctxs[q]->t & 1] + xq.rd[g] * V, sg.pk_list + xg.sd[q] * V,
-                                sizeof(uint32_t) * V * xq.rc[g], hipMemcpyDeviceToDevice, st));
-      }
-      HIPCHECK(gm_launch_partial_unpack(dq, ctxs[q]->t, (int)xq.rbase, (int)xq.rrows, st));
-      roff[q] = xq.rbase + xq.rrows;
-    }
-  for (int q = 0; q < G; q++) ctxs[q]->p_recv_last = (int64_t)roff[q];
-  HIPCHECK(hipStreamSynchronize(ls));
+  for (int g = 0; g < G; g++) HIPCHECK(hipStreamSynchronize(ctxs[g]->stream));  // the tick runs on the first member's streams
+  const int rc = tick_partial(ctxs, G);
+  HIPCHECK(hipStreamSynchronize(ctxs[0]->stream));
+  HIPCHECK(hipStreamSynchronize(ctxs[0]->p_side));  // the prefetch writes every member's S2 buffer
+  TRY(rc);
   for (int g = 0; g < G; g++) {
     TRY(check_err(ctxs[g]));
-    ctxs[g]->t++;
-    ctxs[g]->ticks_done++;
-    ctxs[g]->undrained = true;
+    advance(ctxs[g]);
   }
   return GM_OK;
 }

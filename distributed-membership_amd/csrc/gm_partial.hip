@@ -994,16 +994,6 @@ hipError_t gm_launch_partial_chunk(const PState &s, int t, const uint32_t *mtraw
   return hipGetLastError();
 }
 
-hipError_t gm_launch_partial_tick(const PState &s, int t, uint32_t *mtraw, hipStream_t st, hipEvent_t k0,
-                                  hipEvent_t k1) {
-  hipError_t e = gm_launch_partial_mtgen(s, t, mtraw, st, true);
-  if (e != hipSuccess) return e;
-  if (k0) (void)hipEventRecord(k0, st);
-  for (int c = 0; c < s.nchunk && e == hipSuccess; c++) e = gm_launch_partial_chunk(s, t, mtraw, c, st);
-  if (k1) (void)hipEventRecord(k1, st);
-  return e != hipSuccess ? e : hipGetLastError();
-}
-
 hipError_t gm_launch_partial_init(const PState &s, int t0, uint64_t init_seed, hipStream_t st) {
   hipLaunchKernelGGL(gm_p_init, dim3((s.nloc + 63) / 64), dim3(64), 0, st, s, t0, init_seed);
   return hipGetLastError();

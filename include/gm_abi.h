@@ -320,7 +320,8 @@ int gm_last_kernel_ms(gm_ctx *ctx, float *ms);
  * ncclAllReduce(MAX) of resolved draws -> acceptance} until every row has its
  * gossip targets (stream-ordered bounded rounds; rows they cannot take finish in host-driven
  * rounds before the tick is read or the next one starts). No gossip payload crosses GPUs. The phase functions expose
- * the same steps for G contexts on one device (gm_shard_loopback collectives). */
+ * the same steps for G contexts on one device (gm_shard_loopback: the tick's own collectives
+ * over a group of G contexts). */
 int gm_comm_unique_id(uint8_t *out128);   /* ncclGetUniqueId, on one rank */
 /* ncclCommInitRank, then an all-gather of the config words every rank must share (mode, n,
  * band, view, GM_CHUNKS, seeds, drop schedule, init state): GM_EINVAL if any rank differs.
@@ -337,10 +338,15 @@ int gm_shard_end_tick(gm_ctx *ctx);
 /* what = 0: all-gather the per-row counts; what = 1: MAX-allreduce the first n*D draws;
  * what = 2 (msgcount recording, after what = 0): SUM-allreduce this tick's fresh counts */
 int gm_shard_loopback(gm_ctx **ctxs, int32_t G, int32_t what, int32_t D);
-/* One whole tick of G column-shard contexts on one device in the chunk order of the pipelined
- * RCCL tick (per exchange row chunk: all-gather of the counts, round-0 draws, MAX-reduce, acceptance;
- * then the bounded rounds 1, 2), the collectives by device copies. Not for the join ramp or msgcount
- * recording (GM_EINVAL); rows the bounded rounds cannot take return GM_ERANGE (use the phase API). */
+/* One whole tick of the G column-shard contexts of one cluster on one device: the sharded tick
+ * gm_tick runs per rank (the same host code over the group of G contexts, on the first context's
+ * streams), its collectives done by device copies and reduce kernels instead of RCCL. It takes
+ * gm_tick's decisions: pipelined over the exchange row chunks with the bounded rounds 1, 2 run only
+ * when round 0 left rows pending, or the host-driven draw loop under mass failure / heavy loss
+ * (GM_SHARD_SYNC). The tick is complete when the call returns: rows the bounded rounds cannot take
+ * finish in host-driven rounds here (gm_tick leaves them to the next call on the context), and
+ * shards that count different pending rows return GM_ESTATE. Not for the join ramp or msgcount
+ * recording (GM_EINVAL; use the phase API). */
 int gm_shard_loopback_tick(gm_ctx **ctxs, int32_t G);
 /* Host-collective hook: the exchange buffers of ONE column-shard context as host arrays, so a
  * host-side collective (e.g. gloo between processes) can stand in for RCCL or gm_shard_loopback
@@ -365,7 +371,11 @@ int gm_shard_stub(gm_ctx *ctx, int32_t on);
  * ncclAllToAllv of fixed-size blocks (record headers stamped with the tick; the lists'
  * fresh entries, 4 bytes each, read in place by the next tick) -- sizes come from the
  * shard layout, so no host round trip -- then appends the received records to their
- * targets' inboxes. gm_partial_loopback_tick does one such tick for G contexts on one device. */
+ * targets' inboxes. After every change of the crash set the ranks agree on its hash (the block
+ * sizes follow from it); a rank holding another set latches GM_ESTATE. gm_partial_loopback_tick runs
+ * the same tick (the same host code) over the G contexts of one cluster on one device, the block
+ * exchange by device copies and the agreement on the host, where it latches GM_ESTATE on all G; a
+ * device error of the tick (an overflowing block: GM_ERANGE) is returned by the call. */
 int gm_partial_loopback_tick(gm_ctx **ctxs, int32_t G);
 /* bytes this shard received from the other shards in the last tick's exchange (whole blocks) */
 int gm_shard_exchange_bytes(gm_ctx *ctx, int64_t *bytes);

@@ -27,8 +27,8 @@ def main():
     ap.add_argument("--ticks", type=int, default=20)
     ap.add_argument("--prologue", type=int, default=28)
     ap.add_argument("--pipelined", action="store_true",
-                    help="time gm_shard_loopback_tick (the pipelined RCCL tick's chunk order, one stream) "
-                         "instead of the phase-API loopback")
+                    help="time gm_shard_loopback_tick (gm_tick's sharded tick over the group of G contexts, the "
+                         "collectives by device copies) instead of the phase-API loopback")
     a = ap.parse_args()
     load_library()
     n, G = a.cluster, a.shards

@@ -218,6 +218,39 @@ def test_packed_block_overflow_fails_loudly(monkeypatch):
     assert e.value.code == -4
 
 
+@pytest.mark.parametrize("seeds", [(42, 42), (42, 43)])
+def test_row_shards_crash_set_disagreement_latches(seeds, monkeypatch):
+    """Row shards given different crash sets would size their exchange blocks differently. At
+    n = 300, two shards, one chunk, every block's capacity equals its row count whatever the crash
+    set, so the block size check cannot see it: the crash-set hash agreement of the tick must, and
+    it latches GM_ESTATE on every member of the group. The same set on both shards (the control)
+    runs clean."""
+    from membership.abi import GmError, partial_loopback_tick
+    n, world = 300, 2
+    monkeypatch.setenv("GM_CHUNKS", "1")
+    monkeypatch.delenv("GM_XCHG_CAP_FRAC", raising=False)
+    sh = [Simulator(n, GM_MODE_PARTIAL, rd_seed=7, view=16, view_seed=5, init_mode=1, init_t0=8, init_seed=11,
+                    shard_rank=g, shard_count=world) for g in range(world)]
+    for _ in range(4):
+        partial_loopback_tick(sh)
+    sets = [crash_set(n, 6, seed) for seed in seeds]
+    assert np.array_equal(sets[0], sets[1]) == (seeds[0] == seeds[1])
+    for s, crash in zip(sh, sets):
+        s.set_failed(crash)
+    if seeds[0] == seeds[1]:
+        for _ in range(4):
+            partial_loopback_tick(sh)
+        assert all(s.tick_stats()["err"] == 0 for s in sh)
+        return
+    with pytest.raises(GmError) as e:
+        partial_loopback_tick(sh)
+    assert e.value.code == -5
+    for s in sh:
+        with pytest.raises(GmError) as e:
+            s.tick()
+        assert e.value.code == -5
+
+
 @pytest.mark.parametrize("chunks", [1, 4])
 def test_row_shards_contiguous_half_crash_match_single_context(chunks, monkeypatch):
     """The reference's multifailure schedule crashes a contiguous half of the cluster

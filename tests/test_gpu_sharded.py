@@ -89,22 +89,42 @@ def test_pipelined_shards_match_fused_kernel(n, world, drop, chunks, pcap, monke
     and the rows each rank's atomics had put in an overflowing list would differ -- such a list
     is void on every rank and its rows take the host-driven rounds (the full-size S-B run at
     tick 15 found it: ranks MAX-reduced statuses of different rows)."""
-    from membership.abi import shard_loopback_tick
-    monkeypatch.setenv("GM_SCHUNKS", str(chunks))
+    env = {"GM_SCHUNKS": str(chunks)}
     if pcap:
-        monkeypatch.setenv("GM_PLIST_CAP", str(pcap))
+        env["GM_PLIST_CAP"] = str(pcap)
+    run_pipelined_shards(n, world, drop, max(2, n // 64), 34, env, monkeypatch)
+
+
+@pytest.mark.parametrize("sync", ["0", None])
+def test_pipelined_shards_half_cluster_crash(sync, monkeypatch):
+    """Half the cluster crashed at tick 8 (n = 777, three shards, three exchange chunks): the two
+    decisions of the sharded tick no other multi-rank case takes. GM_SHARD_SYNC=0 keeps the bounded
+    path: round 0 leaves many rows pending, so the deferred rounds 1 and 2 run from the settle
+    with a real 3-way MAX-reduce. Unset, 10 * nfailed > n selects the host-driven loop, so
+    gm_shard_loopback_tick takes the sync path over a group of three."""
+    env = {"GM_SCHUNKS": "3"}
+    if sync is not None:
+        env["GM_SHARD_SYNC"] = sync
+    run_pipelined_shards(777, 3, 0, 388, 24, env, monkeypatch)
+
+
+def run_pipelined_shards(n, world, drop, ncrash, ticks, env, monkeypatch):
+    from membership.abi import shard_loopback_tick
+    monkeypatch.delenv("GM_SHARD_SYNC", raising=False)
+    for k, v in env.items():  # read at context creation
+        monkeypatch.setenv(k, v)
     kw = dict(rd_seed=7, drop_pct=drop, drop_from=3, drop_to=25, drop_seed=42, init_mode=1, init_t0=6, init_seed=5)
     ref = Simulator(n, GM_MODE_SCALED, **kw)
     shards = [Simulator(n, GM_MODE_SCALED, shard_rank=g, shard_count=world, **kw) for g in range(world)]
     phase = [Simulator(n, GM_MODE_SCALED, shard_rank=g, shard_count=world, **kw) for g in range(world)]
-    monkeypatch.delenv("GM_SCHUNKS")
-    monkeypatch.delenv("GM_PLIST_CAP", raising=False)
+    for k in env:
+        monkeypatch.delenv(k)
     owners = np.zeros(n, dtype=int)
     for g, s in enumerate(shards):
         c0, w = s.shard_layout()
         owners[c0:c0 + w] = g
-    crash = crash_set(n, max(2, n // 64), 42)
-    for _ in range(34):
+    crash = crash_set(n, ncrash, 42)
+    for _ in range(ticks):
         t = ref.time
         ref.tick()
         shard_loopback_tick(shards)
