@@ -48,6 +48,8 @@ hipError_t gm_launch_msgcount(const SState &s, int t, bool dropped, int phase, h
 hipError_t gm_launch_detect(const SState &s, gm_detect_rec *rec, uint64_t *timeline, int t, hipStream_t st);
 hipError_t gm_launch_census(const SState &s, gm_census_rec *rec, uint64_t *hist, uint32_t *status, int T,
                             hipStream_t st);
+hipError_t gm_launch_view_census(const PState &s, const uint32_t *cls, void *acc, gm_view_rec *rec, uint64_t *hist,
+                                 uint64_t *sizes, uint32_t *status, int T, hipStream_t st);
 hipError_t gm_launch_load_check(const SState &s, int t, int r0, int cnt, const int32_t *hb, const int32_t *ts,
                                 int32_t *base, int32_t *own, uint32_t *status, hipStream_t st);
 hipError_t gm_launch_load_encode(const SState &s, int t, int r0, int cnt, const int32_t *hb, const int32_t *ts,
@@ -114,6 +116,12 @@ struct gm_ctx {
   // SCALED census (gm_census): device scratch, allocated by the first call -- the records [s.w], the
   // histogram, the kernels' status word
   uint8_t *cen_blob = nullptr;
+  // PARTIAL view census (gm_view_census): device scratch, allocated on first use. vc_blob: the per-subject
+  // accumulators [n] (16 bytes each), the two histograms, the kernels' status word and the crash bitmap of the
+  // cluster, rebuilt from failed_h when the crash set has changed; vc_rec: the records [n], once a call asks for them
+  uint8_t *vc_blob = nullptr;
+  gm_view_rec *vc_rec = nullptr;
+  int64_t vc_nfailed = -1;           // nfailed when the bitmap was last built (-1: never)
   // FAITHFUL
   FState f{};
   size_t f_smem = 0;
@@ -1458,6 +1466,49 @@ extern "C" int gm_census(gm_ctx *c, gm_census_rec *out, uint64_t *hist) {
   }
   if (out) HIPCHECK(ctx_memcpy(c, out, d_rec, rec_bytes, hipMemcpyDeviceToHost));
   if (hist) HIPCHECK(ctx_memcpy(c, hist, d_hist, hist_bytes, hipMemcpyDeviceToHost));
+  return GM_OK;
+}
+
+// PARTIAL: the view census of the state as of the last tick (gm_view_census.hip). A read-back: it
+// waits for the enqueued ticks, reports their device error, and writes nothing but its own scratch.
+extern "C" int gm_view_census(gm_ctx *c, gm_view_rec *out, uint64_t *hist, uint64_t *sizes) {
+  if (!c || (!out && !hist && !sizes)) return GM_EINVAL;
+  if (c->cfg.mode != GM_MODE_PARTIAL) return GM_EUNSUPPORTED;
+  if (c->latched != GM_OK) return c->latched;
+  if (c->p_comm) HIPCHECK(hipStreamSynchronize(c->p_comm));  // a row shard's exchange and unpacks
+  TRY(check_err(c));  // waits for the stream
+  const PState &p = c->p;
+  const size_t n = (size_t)p.n;
+  const size_t acc_bytes = 16 * n, hist_bytes = sizeof(uint64_t) * 2 * GM_VIEW_AGES;
+  const size_t sizes_bytes = sizeof(uint64_t) * GM_VIEW_SIZES, cls_words = (n + 31) / 32;
+  const size_t zero_bytes = acc_bytes + hist_bytes + sizes_bytes + sizeof(uint64_t);  // all but the bitmap
+  if (!c->vc_blob) TRY(dalloc(c, &c->vc_blob, zero_bytes + sizeof(uint32_t) * cls_words));
+  if (out && !c->vc_rec) TRY(dalloc(c, &c->vc_rec, n));
+  uint64_t *d_hist = (uint64_t *)(c->vc_blob + acc_bytes);
+  uint64_t *d_sizes = (uint64_t *)(c->vc_blob + acc_bytes + hist_bytes);
+  uint32_t *d_status = (uint32_t *)(c->vc_blob + acc_bytes + hist_bytes + sizes_bytes);
+  uint32_t *d_cls = (uint32_t *)(c->vc_blob + zero_bytes);
+  HIPCHECK(ctx_memset(c, c->vc_blob, 0, zero_bytes));
+  if (c->vc_nfailed != c->nfailed) {  // the subjects' classes: every shard is given the whole crash set.
+    // PARTIAL crash flags are only ever set, so the count of set flags names the set the bitmap holds
+    std::vector<uint32_t> cls(cls_words, 0u);
+    if (c->nfailed)
+      for (size_t i = 0; i < n; i++)
+        if (c->failed_h[i]) cls[i >> 5] |= 1u << (i & 31);
+    HIPCHECK(ctx_memcpy(c, d_cls, cls.data(), sizeof(uint32_t) * cls_words, hipMemcpyHostToDevice));
+    c->vc_nfailed = c->nfailed;
+  }
+  HIPCHECK(gm_launch_view_census(p, d_cls, c->vc_blob, out ? c->vc_rec : nullptr, d_hist, d_sizes, d_status, c->t - 1,
+                                 c->stream));
+  uint32_t st = 0;
+  HIPCHECK(ctx_memcpy(c, &st, d_status, sizeof st, hipMemcpyDeviceToHost));
+  if (st) {
+    snprintf(g_errbuf, sizeof g_errbuf, "gm_view_census: a stored view cannot be right (flags 0x%x: 1 id, 2 heartbeat, 4 age)", st);
+    return GM_ESTATE;
+  }
+  if (out) HIPCHECK(ctx_memcpy(c, out, c->vc_rec, sizeof(gm_view_rec) * n, hipMemcpyDeviceToHost));
+  if (hist) HIPCHECK(ctx_memcpy(c, hist, d_hist, hist_bytes, hipMemcpyDeviceToHost));
+  if (sizes) HIPCHECK(ctx_memcpy(c, sizes, d_sizes, sizes_bytes, hipMemcpyDeviceToHost));
   return GM_OK;
 }
 

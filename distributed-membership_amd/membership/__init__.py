@@ -11,4 +11,5 @@ from .abi import (GM_EV_JOINED, GM_EV_REMOVED, GM_EV_START_GROUP, GM_EV_TIME_MAR
 from .app import Application, Params, format_msgcount, log_addr  # noqa: F401
 from .detect import summarize  # noqa: F401
 from .census import merge_shards, summarize_census  # noqa: F401
+from .views import merge_view_shards, summarize_views  # noqa: F401
 from . import state  # noqa: F401

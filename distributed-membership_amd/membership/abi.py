@@ -57,6 +57,16 @@ CENSUS_DTYPE = np.dtype([("hb_min", "<i4"), ("hb_max", "<i4"), ("ts_min", "<i4")
                          ("holders", "<u4"), ("stale", "<u4"), ("hb_sum", "<u8"), ("ts_sum", "<u8")])
 assert CENSUS_DTYPE.itemsize == ctypes.sizeof(GmCensusRec) == 40
 
+class GmViewRec(ctypes.Structure):
+    _fields_ = [("hb_min", ctypes.c_int32), ("hb_max", ctypes.c_int32), ("holders", ctypes.c_uint32),
+                ("stale", ctypes.c_uint32), ("hb_sum", ctypes.c_uint64)]
+
+
+# gm_view_rec as a NumPy structured dtype (24 bytes, the field names of include/gm_abi.h)
+GM_VIEW_AGES, GM_VIEW_SIZES = 32, 33
+VIEW_DTYPE = np.dtype([("hb_min", "<i4"), ("hb_max", "<i4"), ("holders", "<u4"), ("stale", "<u4"), ("hb_sum", "<u8")])
+assert VIEW_DTYPE.itemsize == ctypes.sizeof(GmViewRec) == 24
+
 EXPORTS = ["gm_detect_record", "gm_detect", "gm_detect_timeline", "gm_parse_conf", "gm_create", "gm_destroy", "gm_tick", "gm_sync", "gm_time", "gm_rand", "gm_set_failed",
            "gm_set_dropmsg", "gm_drain_events", "gm_event_counts", "gm_msgcount", "gm_read_row", "gm_read_table", "gm_read_nodes",
            "gm_dump_tables", "gm_tick_stats", "gm_set_timing", "gm_last_kernel_ms", "gm_crash_set", "gm_strerror",
@@ -64,7 +74,7 @@ EXPORTS = ["gm_detect_record", "gm_detect", "gm_detect_timeline", "gm_parse_conf
            "gm_shard_accept", "gm_shard_end_tick", "gm_shard_loopback", "gm_partial_loopback_tick",
            "gm_shard_exchange_bytes", "gm_keep_events", "gm_event_totals", "gm_read_views", "gm_shard_stub",
            "gm_msgcount_record", "gm_comm_info", "gm_shard_export", "gm_shard_import", "gm_pool_info", "gm_shard_loopback_tick", "gm_read_targets",
-           "gm_load_begin", "gm_load_rows", "gm_load_commit", "gm_load_stats", "gm_census"]
+           "gm_load_begin", "gm_load_rows", "gm_load_commit", "gm_load_stats", "gm_census", "gm_view_census"]
 
 _lib = None
 
@@ -121,6 +131,7 @@ def load_library():
         "gm_load_commit": [ctypes.c_void_p, P(i32), P(i32), P(i32), P(i32)],
         "gm_load_stats": [ctypes.c_void_p, P(ctypes.c_double)],
         "gm_census": [ctypes.c_void_p, P(GmCensusRec), P(u64)],
+        "gm_view_census": [ctypes.c_void_p, P(GmViewRec), P(u64), P(u64)],
     }
     # GM_AB_BUILD=1 (A/B scripts only): an older measurement build may lack newer entry points, which
     # are then left unbound. Otherwise every entry point must be present, whatever library GM_LIBRARY
@@ -313,6 +324,20 @@ class Simulator:
         self._call("gm_census", self.h, rec.ctypes.data_as(ctypes.POINTER(GmCensusRec)) if records else None,
                    _ptr(h, ctypes.c_uint64) if hist else None)
         return rec, h
+
+    def view_census(self, records=True):
+        """PARTIAL: the census of the stored views as of the last tick, reduced on the device
+        (gm_view_census). Returns (rec, hist, sizes): rec a VIEW_DTYPE array, one record per subject
+        node of the whole cluster (holders, stale, hb min / max / sum over the live observers'
+        entries; a row shard counts its own nodes' views), or None with records=False; hist uint64
+        [2, GM_VIEW_AGES], the live observers' entries by (subject's crash flag, age); sizes uint64
+        [GM_VIEW_SIZES], the live observers by view size."""
+        rec = np.zeros(self.n, dtype=VIEW_DTYPE) if records else None
+        hist = np.zeros((2, GM_VIEW_AGES), dtype=np.uint64)
+        sizes = np.zeros(GM_VIEW_SIZES, dtype=np.uint64)
+        self._call("gm_view_census", self.h, rec.ctypes.data_as(ctypes.POINTER(GmViewRec)) if records else None,
+                   _ptr(hist, ctypes.c_uint64), _ptr(sizes, ctypes.c_uint64))
+        return rec, hist, sizes
 
     def read_row(self, r, c0=0, length=None):
         length = self.n if length is None else length

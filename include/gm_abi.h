@@ -294,6 +294,32 @@ typedef struct gm_census_rec {   /* 40 bytes, one per subject column of this con
  * stored state whose escape lists disagree with its cells: GM_ESTATE. */
 int gm_census(gm_ctx *ctx, gm_census_rec *out, uint64_t *hist);
 
+/* ---- PARTIAL: the view census, reduced on the device (the views are not copied to the host). */
+#define GM_VIEW_AGES  32
+#define GM_VIEW_SIZES 33          /* view sizes 0..32 (P_VMAX) */
+typedef struct gm_view_rec {      /* 24 bytes, one per subject node of the CLUSTER (index = id - 1) */
+  int32_t  hb_min, hb_max;        /* over the entries counted in holders; -1 = none */
+  uint32_t holders;               /* live observers (failed == 0) whose view holds the subject;
+                                     a live node's own entry counts */
+  uint32_t stale;                 /* of those, entries with T - (hb+1)/2 >= TFAIL */
+  uint64_t hb_sum;
+} gm_view_rec;
+/* PARTIAL. The state as of the last tick run, T = gm_time - 1 (after create: as created, T = init_t0).
+ * The views are exactly what gm_read_views returns; a view whose observer has failed != 0 is frozen
+ * and contributes nothing to any output. out[n] over all subjects of the cluster;
+ * hist[2][GM_VIEW_AGES]: entries of live observers by (subject's crash flag as given to
+ * gm_set_failed, age = T - (hb + 1) / 2 -- the timestamp is derived from the heartbeat, so age and
+ * heartbeat lag are one number); sizes[GM_VIEW_SIZES]: live observers by the entries their view holds.
+ * Any of the three pointers may be NULL, not all. A row shard reduces its own nodes' views over all n
+ * subjects: the shards' holders / stale / hb_sum / hist / sizes add up to the cluster's, hb_min /
+ * hb_max combine by min / max over the shards that hold the subject (membership.merge_view_shards).
+ * The call is a read-back: it waits for the enqueued ticks (both streams of a row shard), reports a
+ * latched device error and changes nothing a later tick or read observes; its device scratch is
+ * allocated by the first call and freed by gm_destroy. FAITHFUL / SCALED: GM_EUNSUPPORTED. A stored
+ * entry that cannot be right -- an id outside [1, n], an even heartbeat, a heartbeat above 2T - 1, an
+ * age >= GM_VIEW_AGES (the sweep removes at age 20) -- : GM_ESTATE, no output written. */
+int gm_view_census(gm_ctx *ctx, gm_view_rec *out, uint64_t *hist, uint64_t *sizes);
+
 /* Render the membership lists of every node in the parity dump format
  * ("t i inited inGroup bFailed heartbeat n id:hb:ts ...\n" per node). */
 int gm_dump_tables(gm_ctx *ctx, char *buf, size_t cap, size_t *len);

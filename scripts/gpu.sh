@@ -20,6 +20,8 @@
 #   mix_sc     SQ instruction mix / wave-cycle split of S-C (one --pmc pass) -> $O/mix_sc/
 #   faithful   ./Application on the three testcases + N = 70, timed -> $O/faithful_wall.txt
 #   census     scripts/census_cost.py: gm_census at S-A (cost, self-check)  -> $O/census_cost.json
+#   viewcensus scripts/view_census_cost.py: gm_view_census at S-C (cost, self-check) -> $O/view_census_cost.json
+#   prof_viewcensus rocprofv3 --kernel-trace --stats of gm_view_census at S-C, tick 11 -> $O/prof_viewcensus/
 #   prof_faithful rocprofv3 --kernel-trace --stats of ./Application at N = 70 -> $O/prof_n70/
 #
 # Every GPU step runs under its own timeout; steps are chained so the first
@@ -70,6 +72,9 @@ run_step() {
                   echo -n "$c "; { time timeout -k 10 60 ./Application testcases/$c.conf > /dev/null; } 2>&1 || exit 1
                 done ) > $O/faithful_wall.txt 2>&1 ;;
     census) timeout -k 10 420 python -u scripts/census_cost.py --out $O/census_cost.json ${CENSUS_ARGS:-} > $O/census_cost.txt 2> $O/census_cost.err ;;
+    viewcensus) timeout -k 10 900 python -u scripts/view_census_cost.py --out $O/view_census_cost.json ${VIEWCENSUS_ARGS:-} > $O/view_census_cost.txt 2> $O/view_census_cost.err ;;
+    prof_viewcensus) timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_viewcensus -o vc -- \
+               python3 scripts/view_census_cost.py --kernels-only > $O/prof_viewcensus.log 2>&1 ;;
     prof_faithful) timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_n70 -o n70 -- \
                ./Application testcases/n70.conf > $O/prof_n70.log 2>&1 ;;
     *) echo "unknown step $1"; return 2 ;;
