@@ -58,6 +58,8 @@ hipError_t gm_launch_load_nodes(const SState &s, int t, const int32_t *heartbeat
                                 const int32_t *targets, const int32_t *counts, const int32_t *own, uint32_t *status,
                                 int write, hipStream_t st);
 hipError_t gm_launch_load_inbox(const SState &s, int t, uint32_t *status, hipStream_t st);
+hipError_t gm_launch_read_decode(const SState &s, int par, int r0, int rows, int32_t *stage, uint32_t *status,
+                                 hipStream_t st);
 size_t gm_partial_lds_bytes();
 
 #define GM_T_LIMIT 32766  // packed 16-bit hb/ts stay exact: hb <= 2t+1 < 0xFFFF
@@ -145,6 +147,13 @@ struct gm_ctx {
   int64_t ld_rows = 0;
   double ld_ms[2] = {0, 0};          // gm_set_timing on: ms in gm_l_check / gm_l_encode since gm_load_begin
   hipEvent_t ld_ev[3] = {nullptr, nullptr, nullptr};
+  // SCALED rows decoded on the device (gm_read_rows): one device block, allocated by the first call and
+  // reused -- the staging planes hb, ts [rd_cap][w] of one decode launch, then the kernel's status word
+  uint8_t *rd_blob = nullptr;
+  int rd_cap = 0;                    // rows per decode launch
+  int64_t rd_rows = 0;               // rows decoded since gm_create
+  double rd_ms[2] = {0, 0};          // gm_set_timing on: ms in gm_r_decode / in the device-to-host copies
+  hipEvent_t rd_ev[3] = {nullptr, nullptr, nullptr};
   // PARTIAL
   PState p{};
   uint32_t *p_mtraw = nullptr;        // [2][nloc][16] S2 outputs by tick parity
@@ -796,6 +805,8 @@ extern "C" int gm_destroy(gm_ctx *c) {
   for (void *p : c->allocs) (void)hipFree(p);
   if (c->ld_blob) (void)hipFree(c->ld_blob);
   for (hipEvent_t e : c->ld_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->rd_ev)
     if (e) (void)hipEventDestroy(e);
   if (c->draw_left_h) (void)hipHostFree(c->draw_left_h);
   if (c->draw_ev) (void)hipEventDestroy(c->draw_ev);
@@ -1748,6 +1759,74 @@ extern "C" int gm_read_table(gm_ctx *c, int32_t r0, int32_t count, int32_t *hb, 
     memcpy(hb + (size_t)i * w, rh.data(), sizeof(int32_t) * w);
     memcpy(ts + (size_t)i * w, rt.data(), sizeof(int32_t) * w);
   }
+  return GM_OK;
+}
+
+// ------------------------------------------------------------------ SCALED rows decoded on the device
+// gm_read_rows (gm_read.hip has the kernel and what it checks): what gm_read_table returns, at a cost
+// that follows count, not n. A read-back: it settles the enqueued ticks, reports their device error,
+// and writes nothing but its own staging block.
+#define GM_READ_STAGE_BYTES (256ull << 20)  // the (hb, ts) planes of one decode launch
+
+extern "C" int gm_read_rows(gm_ctx *c, int32_t r0, int32_t count, int32_t *hb, int32_t *ts) {
+  if (!c) return GM_EINVAL;
+  if (c->cfg.mode != GM_MODE_SCALED) return GM_EUNSUPPORTED;
+  if (r0 < 0 || count < 0 || r0 + (int64_t)count > c->n || (count > 0 && (!hb || !ts))) return GM_EINVAL;
+  if (c->loading) return GM_ESTATE;  // between gm_load_begin and gm_load_commit
+  if (c->latched != GM_OK) return c->latched;
+  TRY(draw_settle(&c, 1));
+  TRY(check_err(c));  // waits for the stream
+  if (count == 0) return GM_OK;
+  const SState &s = c->s;
+  const size_t w = (size_t)s.w, row_bytes = 2 * sizeof(int32_t) * w;
+  if (!c->rd_blob) {
+    size_t cap = std::min<size_t>((size_t)c->n, std::max<size_t>(1, GM_READ_STAGE_BYTES / row_bytes));
+    if (getenv("GM_READ_STAGE_ROWS"))  // diagnostics (tests): smaller decode launches
+      cap = std::max<size_t>(1, std::min<size_t>(cap, (size_t)atol(getenv("GM_READ_STAGE_ROWS"))));
+    TRY(dalloc(c, &c->rd_blob, cap * row_bytes + 16));
+    c->rd_cap = (int)cap;
+  }
+  int32_t *stage = (int32_t *)c->rd_blob;
+  uint32_t *d_status = (uint32_t *)(c->rd_blob + (size_t)c->rd_cap * row_bytes);
+  if (c->timing)
+    for (hipEvent_t &e : c->rd_ev)
+      if (!e) HIPCHECK(hipEventCreate(&e));
+  HIPCHECK(ctx_memset(c, d_status, 0, sizeof(uint32_t)));
+  const int par = (c->t - 1) & 1;
+  for (int off = 0; off < count; off += c->rd_cap) {
+    const int m = std::min(c->rd_cap, count - off);
+    if (c->timing) HIPCHECK(hipEventRecord(c->rd_ev[0], c->stream));
+    HIPCHECK(gm_launch_read_decode(s, par, r0 + off, m, stage, d_status, c->stream));
+    if (c->timing) HIPCHECK(hipEventRecord(c->rd_ev[1], c->stream));
+    uint32_t st = 0;  // nothing of the block is handed out before its checks pass
+    HIPCHECK(ctx_memcpy(c, &st, d_status, sizeof st, hipMemcpyDeviceToHost));
+    if (st) {
+      snprintf(g_errbuf, sizeof g_errbuf, "gm_read_rows: the stored state is inconsistent (flags 0x%x)", st);
+      return GM_ESTATE;
+    }
+    HIPCHECK(ctx_memcpy(c, hb + (size_t)off * w, stage, sizeof(int32_t) * m * w, hipMemcpyDeviceToHost));
+    HIPCHECK(ctx_memcpy(c, ts + (size_t)off * w, stage + (size_t)m * w, sizeof(int32_t) * m * w, hipMemcpyDeviceToHost));
+    if (c->timing) {
+      float a = 0, b = 0;
+      HIPCHECK(hipEventRecord(c->rd_ev[2], c->stream));
+      HIPCHECK(hipEventSynchronize(c->rd_ev[2]));
+      HIPCHECK(hipEventElapsedTime(&a, c->rd_ev[0], c->rd_ev[1]));
+      HIPCHECK(hipEventElapsedTime(&b, c->rd_ev[1], c->rd_ev[2]));
+      c->rd_ms[0] += a;
+      c->rd_ms[1] += b;
+    }
+    c->rd_rows += m;
+  }
+  return GM_OK;
+}
+
+extern "C" int gm_read_rows_stats(gm_ctx *c, double stats[4]) {
+  if (!c || !stats) return GM_EINVAL;
+  if (c->cfg.mode != GM_MODE_SCALED) return GM_EUNSUPPORTED;
+  stats[0] = (double)c->rd_rows;
+  stats[1] = (double)c->rd_cap * 2 * sizeof(int32_t) * (double)c->s.w;
+  stats[2] = c->rd_ms[0];
+  stats[3] = c->rd_ms[1];
   return GM_OK;
 }
 

@@ -74,7 +74,8 @@ EXPORTS = ["gm_detect_record", "gm_detect", "gm_detect_timeline", "gm_parse_conf
            "gm_shard_accept", "gm_shard_end_tick", "gm_shard_loopback", "gm_partial_loopback_tick",
            "gm_shard_exchange_bytes", "gm_keep_events", "gm_event_totals", "gm_read_views", "gm_shard_stub",
            "gm_msgcount_record", "gm_comm_info", "gm_shard_export", "gm_shard_import", "gm_pool_info", "gm_shard_loopback_tick", "gm_read_targets",
-           "gm_load_begin", "gm_load_rows", "gm_load_commit", "gm_load_stats", "gm_census", "gm_view_census"]
+           "gm_load_begin", "gm_load_rows", "gm_load_commit", "gm_load_stats", "gm_census", "gm_view_census",
+           "gm_read_rows", "gm_read_rows_stats"]
 
 _lib = None
 
@@ -132,6 +133,8 @@ def load_library():
         "gm_load_stats": [ctypes.c_void_p, P(ctypes.c_double)],
         "gm_census": [ctypes.c_void_p, P(GmCensusRec), P(u64)],
         "gm_view_census": [ctypes.c_void_p, P(GmViewRec), P(u64), P(u64)],
+        "gm_read_rows": [ctypes.c_void_p, i32, i32, P(i32), P(i32)],
+        "gm_read_rows_stats": [ctypes.c_void_p, P(ctypes.c_double)],
     }
     # GM_AB_BUILD=1 (A/B scripts only): an older measurement build may lack newer entry points, which
     # are then left unbound. Otherwise every entry point must be present, whatever library GM_LIBRARY
@@ -354,6 +357,36 @@ class Simulator:
         ts = np.zeros((count, w), dtype=np.int32)
         self._call("gm_read_table", self.h, r0, count, _ptr(hb), _ptr(ts))
         return hb, ts
+
+    def read_rows(self, r0=0, count=None, out=None):
+        """SCALED: what read_table returns -- (hb, ts) int32 [count][w] of rows [r0, r0 + count) over this
+        context's columns, -1 = absent -- decoded on the device (gm_read_rows): only the rows asked
+        for cross to the host. out = (hb, ts): C-contiguous int32 arrays of at least count * w elements
+        each to decode into (a caller reading block by block reuses one pair); the returned arrays are
+        views of their first count rows."""
+        count = self.n - r0 if count is None else count
+        w = self.shard_layout()[1] if self.mode == GM_MODE_SCALED else self.n
+        if out is None:
+            hb = np.zeros((max(count, 0), w), dtype=np.int32)
+            ts = np.zeros((max(count, 0), w), dtype=np.int32)
+        else:
+            hb, ts = out
+            for a in (hb, ts):
+                if a.dtype != np.int32 or not a.flags["C_CONTIGUOUS"] or a.size < max(count, 0) * w:
+                    raise ValueError("read_rows: out arrays must be C-contiguous int32 of at least count * w elements")
+        self._call("gm_read_rows", self.h, r0, count, _ptr(hb), _ptr(ts))
+        if out is not None:
+            hb, ts = (a.reshape(-1)[:count * w].reshape(count, w) for a in (hb, ts))
+        return hb, ts
+
+    def read_rows_stats(self):
+        """{"rows", "staging_bytes", "stage_rows", "decode_ms", "copy_ms"} of read_rows since the context
+        was created (the times only while set_timing is on); stage_rows: rows per decode launch"""
+        v = (ctypes.c_double * 4)()
+        self._call("gm_read_rows_stats", self.h, v)
+        w = self.shard_layout()[1]
+        return {"rows": int(v[0]), "staging_bytes": int(v[1]), "stage_rows": int(v[1]) // (8 * w),
+                "decode_ms": float(v[2]), "copy_ms": float(v[3])}
 
     def read_nodes(self):
         rows = self.shard_layout()[1] if self.mode == GM_MODE_PARTIAL else self.n  # a row shard: its own nodes

@@ -13,19 +13,55 @@ A column shard's snapshot holds its own columns and the same node arrays as ever
 except that a shard bumps the heartbeat counters of the nodes whose columns it holds only: its
 `heartbeat` is current for those nodes (which is all a load into that shard checks and uses), and
 join_columns takes each node's counter from the shard that holds its column.
+
+At the sizes the project is built for, the tables do not fit a host's memory comfortably (S-A: two
+17 GB arrays), and read_table copies the whole stored state to the host to decode it there.
+snapshot(device=True) reads through read_rows instead (decoded on the device, block by block);
+save_dir streams a state to a directory block by block, and load_dir returns it with hb / ts
+memory-mapped, which restore loads block by block: the whole table is never in memory.
 """
+import os
+
 import numpy as np
 
 KEYS = ("t", "hb", "ts", "heartbeat", "failed", "targets", "counts")
+NODE_KEYS = ("t", "heartbeat", "failed", "targets", "counts")  # everything but the tables (save_dir's nodes.npz)
 
 
-def snapshot(sim):
-    """The state of a SCALED context between two ticks (a column shard: its own columns)."""
-    hb, ts = sim.read_table()
+def _chunk_rows(w, chunk_rows):
+    """rows per block: as given, else about 64 MiB of (hb, ts) (Simulator.load_state's default)"""
+    return max(1, int(chunk_rows)) if chunk_rows is not None else max(1, (64 << 20) // (8 * w))
+
+
+def _read_blocks(sim, hb, ts, chunk_rows):
+    """rows [0, n) through read_rows into hb / ts [n][w], block by block"""
+    n, w = hb.shape
+    m = min(n, _chunk_rows(w, chunk_rows))
+    buf = (np.empty((m, w), dtype=np.int32), np.empty((m, w), dtype=np.int32))
+    for r0 in range(0, n, m):
+        k = min(m, n - r0)
+        bh, bt = sim.read_rows(r0, k, out=buf)
+        hb[r0:r0 + k] = bh
+        ts[r0:r0 + k] = bt
+
+
+def _nodes(sim):
     st = sim.read_nodes()
     tg, cnt = sim.read_targets()
-    return {"t": int(sim.time), "hb": hb, "ts": ts, "heartbeat": st[:, 3].copy(), "failed": st[:, 2].copy(),
-            "targets": tg, "counts": cnt}
+    return {"t": int(sim.time), "heartbeat": st[:, 3].copy(), "failed": st[:, 2].copy(), "targets": tg, "counts": cnt}
+
+
+def snapshot(sim, device=False, chunk_rows=None):
+    """The state of a SCALED context between two ticks (a column shard: its own columns).
+    device=True: the tables are decoded on the device and read in blocks of chunk_rows rows
+    (read_rows); the default reads them through read_table."""
+    if device:
+        w = sim.shard_layout()[1]
+        hb, ts = np.empty((sim.n, w), dtype=np.int32), np.empty((sim.n, w), dtype=np.int32)
+        _read_blocks(sim, hb, ts, chunk_rows)
+    else:
+        hb, ts = sim.read_table()
+    return dict(_nodes(sim), hb=hb, ts=ts)
 
 
 def restore(sim, snap, chunk_rows=None):
@@ -44,6 +80,33 @@ def load(path):
     with np.load(path) as z:
         snap = {k: z[k].copy() for k in KEYS}
     snap["t"] = int(snap["t"])
+    return snap
+
+
+def save_dir(sim, path, chunk_rows=None):
+    """Stream the state of a SCALED context to the directory `path`: hb.npy / ts.npy (int32 [n][w], written
+    block by block through read_rows, chunk_rows rows at a time) and nodes.npz (t, heartbeat, failed,
+    targets, counts)."""
+    os.makedirs(path, exist_ok=True)
+    w = sim.shard_layout()[1]
+    planes = [np.lib.format.open_memmap(os.path.join(path, name), mode="w+", dtype=np.int32, shape=(sim.n, w))
+              for name in ("hb.npy", "ts.npy")]
+    _read_blocks(sim, planes[0], planes[1], chunk_rows)
+    for p in planes:
+        p.flush()
+    del planes
+    nodes = _nodes(sim)
+    with open(os.path.join(path, "nodes.npz"), "wb") as f:
+        np.savez(f, **{k: np.asarray(nodes[k], dtype=np.int32) for k in NODE_KEYS})
+
+
+def load_dir(path):
+    """The snapshot save_dir wrote, hb / ts memory-mapped read-only (restore loads them block by block)."""
+    with np.load(os.path.join(path, "nodes.npz")) as z:
+        snap = {k: z[k].copy() for k in NODE_KEYS}
+    snap["t"] = int(snap["t"])
+    snap["hb"] = np.load(os.path.join(path, "hb.npy"), mmap_mode="r")
+    snap["ts"] = np.load(os.path.join(path, "ts.npy"), mmap_mode="r")
     return snap
 
 

@@ -225,8 +225,24 @@ int gm_detect_timeline(gm_ctx *ctx, int32_t t, uint64_t *out);
  * columns [c0, c0+len) of this context's shard (c0 relative to the shard start). */
 int gm_read_row(gm_ctx *ctx, int32_t r, int32_t c0, int32_t len, int32_t *hb, int32_t *ts);
 /* Dense readback of observer rows [r0, r0+count): hb/ts [count][w] over this context's
- * w columns (absent -> -1); one bulk copy of the table, for parity tests at larger N. */
+ * w columns (absent -> -1); one bulk copy of the table, for parity tests at larger N. SCALED: the
+ * whole stored state is copied and decoded on the host whatever count is -- at large N read through
+ * gm_read_rows, which returns the same arrays decoded on the device. */
 int gm_read_table(gm_ctx *ctx, int32_t r0, int32_t count, int32_t *hb, int32_t *ts);
+/* SCALED: rows [r0, r0 + count) as gm_read_table returns them -- hb / ts [count][w] over this
+ * context's w columns, -1 = absent -- decoded on the device; only the rows asked for are copied.
+ * The rows are decoded in blocks of max(1, 256 MiB / (8 w)) rows through one device staging buffer
+ * (<= 256 MiB), allocated by the first call, reused, and freed by gm_destroy. Column shards (their own
+ * w columns), join-ramp contexts and contexts recording msgcount or detection are supported. The call
+ * is a read-back: it settles pending draw rounds, waits for the enqueued ticks, reports a latched
+ * device error and changes nothing a later tick or read observes. GM_EINVAL: r0 < 0, count < 0,
+ * r0 + count > n, a NULL array with count > 0 (count == 0 is GM_OK). FAITHFUL / PARTIAL:
+ * GM_EUNSUPPORTED; between gm_load_begin and gm_load_commit: GM_ESTATE; a stored state whose escape
+ * lists disagree with its cells: GM_ESTATE. */
+int gm_read_rows(gm_ctx *ctx, int32_t r0, int32_t count, int32_t *hb, int32_t *ts);
+/* stats = {rows decoded since gm_create, bytes of the staging buffer, and while gm_set_timing is on
+ * the milliseconds spent in the decode kernel and in the device-to-host copies} */
+int gm_read_rows_stats(gm_ctx *ctx, double stats[4]);
 /* PARTIAL: the raw V-entry views (id << 32 | hb, 0 = empty, ascending id) of nodes
  * [r0, r0 + count) as of the last tick, [count][V]; a row shard reads its own nodes. */
 int gm_read_views(gm_ctx *ctx, int32_t r0, int32_t count, uint64_t *out);
