@@ -12,8 +12,11 @@ HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -Wal
 LIB := $(PKG)/lib/libgm.so
 KOBJS := $(PKG)/build/gm_faithful.o $(PKG)/build/gm_scaled.o $(PKG)/build/gm_partial.o $(PKG)/build/gm_detect.o \
          $(PKG)/build/gm_load.o $(PKG)/build/gm_census.o $(PKG)/build/gm_view_census.o $(PKG)/build/gm_read.o \
-         $(PKG)/build/gm_host.o
-HDRS := include/gm_abi.h $(CSRC)/gm_device.h $(CSRC)/gm_faithful.h $(CSRC)/gm_scaled.h $(CSRC)/gm_partial.h
+         $(PKG)/build/gm_host.o $(PKG)/build/gm_host_faithful.o $(PKG)/build/gm_host_scaled.o \
+         $(PKG)/build/gm_host_shard.o $(PKG)/build/gm_host_partial.o $(PKG)/build/gm_host_events.o \
+         $(PKG)/build/gm_host_read.o $(PKG)/build/gm_host_load.o
+HDRS := include/gm_abi.h $(CSRC)/gm_device.h $(CSRC)/gm_faithful.h $(CSRC)/gm_scaled.h $(CSRC)/gm_partial.h \
+        $(CSRC)/gm_host.h
 
 all: $(LIB) Application oracle
 

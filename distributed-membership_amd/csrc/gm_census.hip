@@ -3,12 +3,12 @@
 // A column reduction of the stored table over the live observers: per subject column one
 // gm_census_rec (holders, stale entries, heartbeat / timestamp range and sums) and, over all of this
 // context's columns, the joint histogram of (subject's crash flag, heartbeat lag, age). The table
-// stays on the device; O(w) bytes plus the histogram go back (gm_host.hip gm_census). Nothing the
+// stays on the device; O(w) bytes plus the histogram go back (gm_host_read.hip gm_census). Nothing the
 // tick kernels read is written: the reducer's only outputs are its own scratch.
 //
 // Every live row is relative to the same tick T (wtick[r] == T), so both passes accumulate in cell
 // units (h, age) and convert once per column at the flush: hb = 2T - 255 + h - s_hbase(column),
-// ts = T - age (gm_host.hip decode_scaled_row). A live row holding cells relative to another tick
+// ts = T - age (gm_host_read.hip decode_scaled_row). A live row holding cells relative to another tick
 // sets GM_CEN_ESTATE.
 //
 //   gm_c_bytes  the stored bytes. A workgroup takes one band and a run of rows; a lane owns 4

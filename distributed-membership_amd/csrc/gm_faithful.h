@@ -1,5 +1,6 @@
 // gm_faithful.h -- device state of the FAITHFUL tick (see gm_faithful.hip).
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #define F_ENBUFFSIZE 30000  // EmulNet.h:12
@@ -57,3 +58,12 @@ struct FState {
   int ev_cap;
   uint32_t *err;
 };
+
+// the tick's kernels, in launch order (gm_faithful.hip; launched by gm_host_faithful.hip tick_faithful)
+__global__ void gm_f_recv(FState s, int t);
+__global__ void gm_f_recvout(FState s, int t);
+__global__ void gm_f_node(FState s, int t);
+__global__ void gm_f_sendprep(FState s);
+__global__ void gm_f_s1expand(FState s);
+__global__ void gm_f_sendscan(FState s, int t);
+__global__ void gm_f_sendemit(FState s);

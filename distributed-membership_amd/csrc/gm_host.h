@@ -1,0 +1,291 @@
+// gm_host.h -- internal to libgm's host units (gm_host*.hip): the context, the error plumbing and the
+// functions that cross units. Nothing here is exported: the library's C symbols are include/gm_abi.h's.
+//
+//   gm_host.hip           create / destroy, gm_tick and the small calls, timing ring, error latching
+//   gm_host_faithful.hip  FAITHFUL: state, tick, mailbox collection
+//   gm_host_scaled.hip    SCALED: state, the single-context tick
+//   gm_host_shard.hip     SCALED column shards: RCCL attach, phase API, the sharded tick, loopback
+//   gm_host_partial.hip   PARTIAL: state, tick, the row shards' exchange
+//   gm_host_events.hip    event drains, detection recorder, msgcount
+//   gm_host_read.hip      read-backs: rows, tables, views, nodes, targets, the censuses
+//   gm_host_load.hip      gm_load_*
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "gm_abi.h"
+#include "gm_device.h"
+#include "gm_faithful.h"
+#include "gm_partial.h"
+#include "gm_scaled.h"
+
+#define GM_T_LIMIT 32766  // packed 16-bit hb/ts stay exact: hb <= 2t+1 < 0xFFFF
+#define GM_F_MAILBOX 4096  // FAITHFUL events copied back with the count and error flags
+#define GM_D_FIRST S_MT_RAW  // S2 outputs per row in the first round (steady state needs ~5-6)
+#define GM_D_MORE GM_D_MORE_ROUND  // S2 outputs per row in later rounds (transients with many stale entries)
+#define GM_MAX_ROUNDS 4096    // draw rounds per sharded tick (16 + 64 * 4096 S2 outputs per row)
+#define GM_D_LAST GM_D_LAST_ROUND  // bounded rounds: S2 outputs of round 2 (outputs [80, 336))
+#define GM_SIG_WORDS 17      // gm_comm_init: config words every rank must agree on
+#define GM_TEV_RING 64       // tick-kernel timing: event pairs in the ring (timing_slot)
+
+// detection recorder (gm_detect_record; tmax 0 = off): per-subject records and the per-tick
+// timeline [tmax][3]. SCALED keeps them on the device (gm_s_detect adds each tick's records),
+// FAITHFUL on the host (f_collect)
+struct gm_detect_state {
+  int tmax = 0;
+  gm_detect_rec *rec = nullptr;      // device [s.w]
+  uint64_t *tl = nullptr;            // device [tmax][3]
+  std::vector<gm_detect_rec> rec_h;  // FAITHFUL [n]
+  std::vector<uint64_t> tl_h;        // FAITHFUL [tmax][3]
+};
+
+// SCALED census (gm_census): device scratch, allocated by the first call -- the records [s.w], the
+// histogram, the kernels' status word
+struct gm_census_scratch {
+  uint8_t *blob = nullptr;
+};
+
+// PARTIAL view census (gm_view_census): device scratch, allocated on first use. blob: the per-subject
+// accumulators [n] (16 bytes each), the two histograms, the kernels' status word and the crash bitmap of the
+// cluster, rebuilt from failed_h when the crash set has changed; rec: the records [n], once a call asks for them
+struct gm_view_census_scratch {
+  uint8_t *blob = nullptr;
+  gm_view_rec *rec = nullptr;
+  int64_t nfailed = -1;              // gm_ctx.nfailed when the bitmap was last built (-1: never)
+};
+
+// SCALED state loading (gm_load_begin .. gm_load_commit). One device block (blob, freed by the
+// commit): the staged (hb, ts) of up to cap rows, their base ticks, every row's own entry
+// as staged, the node arrays of the commit, the status word of a call's checks.
+struct gm_load_stage {
+  bool loading = false;              // between gm_load_begin and a successful gm_load_commit
+  bool voided = false;               // a load call failed: only gm_load_begin starts over
+  int t = 0;                         // gm_load_begin's t
+  int cap = 0;                       // staged rows per encode launch
+  void *blob = nullptr;
+  size_t bytes = 0;
+  int32_t *hb = nullptr, *ts = nullptr, *base = nullptr, *own = nullptr, *nodes = nullptr;
+  uint32_t *status = nullptr;
+  std::vector<uint8_t> seen;         // rows given so far
+  int64_t rows = 0;
+  double ms[2] = {0, 0};             // gm_set_timing on: ms in gm_l_check / gm_l_encode since gm_load_begin
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+};
+
+// SCALED rows decoded on the device (gm_read_rows): one device block, allocated by the first call and
+// reused -- the staging planes hb, ts [cap][w] of one decode launch, then the kernel's status word
+struct gm_read_stage {
+  uint8_t *blob = nullptr;
+  int cap = 0;                       // rows per decode launch
+  int64_t rows = 0;                  // rows decoded since gm_create
+  double ms[2] = {0, 0};             // gm_set_timing on: ms in gm_r_decode / in the device-to-host copies
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+};
+
+// FAITHFUL, host side of FState
+struct gm_faithful_host {
+  size_t smem = 0;                   // gm_f_node's dynamic LDS
+  void *mail = nullptr;              // pinned host copy of the FAITHFUL tick mailbox
+  int inflight = 0;                  // FAITHFUL ticks enqueued since the last mailbox collection
+};
+
+// PARTIAL, host side of PState
+struct gm_partial_host {
+  uint32_t *mtraw = nullptr;         // [2][nloc][16] S2 outputs by tick parity
+  hipStream_t side = nullptr;        // S2 outputs of tick t+1, computed while tick t runs
+  hipEvent_t tickev[2] = {nullptr, nullptr};  // by parity: the tick that read that S2 buffer is done
+  hipEvent_t mtev[2] = {nullptr, nullptr};    // by parity: the prefetched S2 outputs are written
+  int mt_next = -1;                  // the tick whose S2 outputs were prefetched
+  int64_t recv_last = 0;             // lists received from other row shards in the last tick
+  bool sharded = false;              // row-shard exchange each tick (G > 1, or one rank forced by GM_FORCE_SHARD=1)
+  std::vector<double> xq;            // per row shard q: probability that a sender addresses q (xcap)
+  uint64_t crash_hash = 0;           // hash of the whole crash set the block capacities were derived from
+  bool crash_check = false;          // agree it across the ranks at the next RCCL tick
+  uint64_t *crash_dev = nullptr;     // [2] device words of that check
+};
+
+// The chunk-pipelined exchange of a sharded tick, SCALED column shards and PARTIAL row shards alike:
+// the exchange of chunk q runs on its own stream once q's kernels are done, while q+1.. still compute
+struct gm_shard_exchange {
+  hipStream_t stream = nullptr;      // RCCL exchange stream (overlaps the next chunk's kernels)
+  std::vector<hipEvent_t> chunk_ev;  // per chunk: its kernels are done (compute stream)
+  hipEvent_t done = nullptr;         // the tick's exchange and what follows it are done (exchange stream)
+};
+
+struct gm_ctx {
+  gm_config cfg;
+  hipStream_t stream = nullptr;
+  int dmax = 0;                      // status exchange depth (sharded)
+  ncclComm_t comm = nullptr;         // RCCL communicator across column shards
+  hipEvent_t k0 = nullptr, k1 = nullptr;  // per-tick band-kernel events (sharded)
+  std::vector<hipEvent_t> tev;            // per-tick band-kernel event pairs (single context)
+  double kernel_ms_sum = 0;
+  int shard_sync = -1;               // sharded tick draw rounds: 1 host-driven unbounded loop, 0 bounded
+  int diag_zero_row = -1;            // diagnostics (GM_DIAG_ZERO_ROW, tests): the pipelined column-shard tick
+                                     //   clears this row's cells after its band kernels, so its records'
+                                     //   counts disagree with the cells and a draw finds no holder
+                                     // stream-ordered, -1 auto (env GM_SHARD_SYNC)
+  int64_t nfailed = 0;               // nodes with failed_h set (gm_set_failed; nodeStart clears it)
+  // sharded bounded draw rounds: rows they could not finish (npending) copied back without a
+  // wait; the next call that needs the tick finishes them with host-driven rounds (draw_settle)
+  int32_t *draw_left_h = nullptr;    // pinned [2]: rows left to the host-driven rounds, rows pending after round 0
+  bool draw_rounds = false;          // the pipelined tick deferred bounded rounds 1, 2 to draw_settle
+  hipEvent_t draw_ev = nullptr;
+  bool draw_check = false;
+  int t = 0;
+  int n = 0;
+  int dropmsg = 0;
+  int latched = GM_OK;
+  bool timing = false;
+  int64_t ticks_done = 0;  // gm_tick calls that enqueued a tick
+  int timed_ticks = 0;  // ticks in the current timing window
+  int ktimed = 0;       // band-kernel event pairs recorded in the window (ring slots in use: min(ktimed, GM_TEV_RING))
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  // events: the device keeps one tick's records; with keep_events (default) a tick's records
+  // are staged to `pending` before the next tick overwrites them (gm_keep_events)
+  bool keep_events = true;
+  bool undrained = false;      // the device holds the last tick's records, not yet staged
+  uint64_t ev_tot[6] = {0, 0, 0, 0, 0, 0};  // FAITHFUL: cumulative records per kind
+  std::vector<gm_event> pending;
+  std::vector<void *> allocs;
+  std::vector<int32_t> failed_h;
+  std::vector<int32_t> fail_t;  // last tick a failed node ran (join ramp: its inGroup is frozen there)
+  gm_detect_state det;
+  FState f{};  // FAITHFUL
+  gm_faithful_host fh;
+  SState s{};  // SCALED
+  gm_census_scratch cen;
+  gm_load_stage ld;
+  gm_read_stage rd;
+  PState p{};  // PARTIAL
+  gm_partial_host ph;
+  gm_view_census_scratch vc;
+  gm_shard_exchange xch;  // SCALED column shards, PARTIAL row shards
+};
+
+namespace gmh {
+extern thread_local char g_errbuf[256];  // gm_strerror's detail (gm_host.hip)
+}
+
+#define HIPCHECK(x)                                                                   \
+  do {                                                                                \
+    hipError_t e_ = (x);                                                              \
+    if (e_ != hipSuccess) {                                                           \
+      snprintf(gmh::g_errbuf, sizeof gmh::g_errbuf, "%s:%d %s", __FILE__, __LINE__, hipGetErrorString(e_)); \
+      return GM_EDEVICE;                                                              \
+    }                                                                                 \
+  } while (0)
+#define NCCLCHECK(x)                                                                 \
+  do {                                                                               \
+    ncclResult_t r_ = (x);                                                           \
+    if (r_ != ncclSuccess) {                                                         \
+      snprintf(gmh::g_errbuf, sizeof gmh::g_errbuf, "%s:%d RCCL %s", __FILE__, __LINE__, ncclGetErrorString(r_)); \
+      return GM_ECOMM;                                                               \
+    }                                                                                \
+  } while (0)
+#define TRY(x)              \
+  do {                      \
+    int r_ = (x);           \
+    if (r_ != GM_OK) return r_; \
+  } while (0)
+
+// Every copy and fill of a context goes through its own stream. That stream is non-blocking, so the
+// legacy null stream that hipMemcpy / hipMemset use neither waits for its kernels nor is waited for by
+// them: a fill at creation could still be running when the init kernel writes (seen as an own entry
+// missing from an S-C view after a 8.6 GB fill of the lists), and a host-to-device copy may return
+// before its DMA lands. Fills are enqueued in order; copies wait for the stream (the host buffers are
+// the caller's).
+static inline hipError_t ctx_memset(gm_ctx *c, void *p, int v, size_t n) { return hipMemsetAsync(p, v, n, c->stream); }
+static inline hipError_t ctx_memcpy(gm_ctx *c, void *d, const void *src, size_t n, hipMemcpyKind k) {
+  const hipError_t e = hipMemcpyAsync(d, src, n, k, c->stream);
+  return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
+}
+static inline hipError_t ctx_memcpy2d(gm_ctx *c, void *d, size_t dpitch, const void *src, size_t spitch, size_t width,
+                                      size_t height, hipMemcpyKind k) {
+  const hipError_t e = hipMemcpy2DAsync(d, dpitch, src, spitch, width, height, k, c->stream);
+  return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
+}
+
+template <class T>
+static int dalloc(gm_ctx *c, T **p, size_t count) {
+  void *q = nullptr;
+  size_t bytes = sizeof(T) * (count ? count : 1);
+  if (hipMalloc(&q, bytes) != hipSuccess) {
+    snprintf(gmh::g_errbuf, sizeof gmh::g_errbuf, "hipMalloc(%zu) failed", bytes);
+    return GM_ENOMEM;
+  }
+  c->allocs.push_back(q);
+  *p = (T *)q;
+  return GM_OK;
+}
+
+// What one host unit defines and another calls.
+namespace gmh {
+
+// gm_host.hip
+void lap(const char *what);  // diagnostics (GM_CREATE_TIMING): where context creation time goes
+int inbox_cap(int cap);
+int exchange_create(gm_ctx *c, int chunks);
+void latch_device_error(gm_ctx *c, uint32_t flags);
+int check_err(gm_ctx *c);
+int f_settle(gm_ctx *c);
+int settled_read(gm_ctx *c);
+int kernel_status(gm_ctx *c, const uint32_t *d_status, int code, const char *fmt, uint32_t *flags = nullptr);
+int timing_slot(gm_ctx *c, hipEvent_t *k0, hipEvent_t *k1, hipStream_t st);
+void advance(gm_ctx *c);
+
+static inline bool drop_tick(const gm_ctx *c, int t) {  // keyed loss applies to the lists sent at t - 1
+  return c->cfg.drop_pct > 0 && t - 1 >= c->cfg.drop_from && t - 1 < c->cfg.drop_to;
+}
+static inline bool mc_on(const gm_ctx *c, int t) { return c->s.mc_sent && t < c->s.mc_tmax; }
+
+// the chunk-major exchange buffer of a column shard (SState.xcnt, S_XC)
+static inline size_t xcnt_bytes(const SState &s) {
+  return sizeof(int32_t) * 2 * (size_t)s.xk * s.shard_count * ((size_t)1 << s.xlog);
+}
+static inline int xchunk_rows(const SState &s, int ch) {  // real rows of exchange chunk ch
+  return (int)std::min<int64_t>((int64_t)1 << s.xlog, (int64_t)s.n - ((int64_t)ch << s.xlog));
+}
+
+// gm_host_faithful.hip
+int create_faithful(gm_ctx *c);
+void destroy_faithful(gm_ctx *c);
+int f_collect(gm_ctx *c);
+int tick_faithful(gm_ctx *c);
+
+// gm_host_scaled.hip
+int create_scaled(gm_ctx *c);
+void destroy_scaled(gm_ctx *c);
+int tick_scaled(gm_ctx *c);
+int ramp_starters(gm_ctx *c, hipStream_t st);
+int detect_tick(gm_ctx *c, int t, hipStream_t st);
+
+// A sharded tick is written once, over a GROUP of local ranks (gm_ctx **g, count G): gm_tick passes
+// {c} (its peers are RCCL ranks, or none under gm_shard_stub), the loopback entry points the G
+// contexts of one cluster living on one device. A tick is a sequence of steps "every member
+// enqueues this launch" separated by group collectives (grp_*, px_*), the only code that differs by
+// group kind. Streams and events are the first member's; buffers and host bookkeeping each member's.
+// gm_host_shard.hip
+int tick_sharded(gm_ctx **g, int G);
+int draw_settle(gm_ctx **g, int G);
+
+// gm_host_partial.hip
+int create_partial(gm_ctx *c);
+void destroy_partial(gm_ctx *c);
+int tick_partial(gm_ctx **g, int G);
+int partial_caps(gm_ctx *c);
+
+// gm_host_events.hip
+int before_tick_events(gm_ctx *c);
+
+// gm_host_load.hip, gm_host_read.hip
+void load_destroy(gm_ctx *c);
+void read_destroy(gm_ctx *c);
+
+}  // namespace gmh

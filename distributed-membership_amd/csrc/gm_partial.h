@@ -1,6 +1,9 @@
 // gm_partial.h -- device state of the PARTIAL-view tick (see gm_partial.hip).
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "gm_abi.h"
 
 #define P_VMAX 32        // view capacity limit (a list is one half-wave of 8-byte entries)
 #define P_KSMALL 12      // nodes with <= P_KSMALL delivered lists take the small-table kernel
@@ -63,7 +66,7 @@ struct PState {
                          //   sent them; the next tick's kernels decode them in place
   // packed exchange blocks (gm_p_pack): chunk c's records to shard q compacted to the front of the
   // rows [q * nloc + r0_c, +cap) of these buffers; only the block's first cap rows travel (cap: the
-  // host's binomial bound from the live nodes per shard, gm_host.hip xcap); rows past the records
+  // host's binomial bound from the live nodes per shard, gm_host_partial.hip xcap); rows past the records
   // keep older stamps, so receivers need no count (gm_p_unpack takes the rows stamped t)
   int32_t *pk_hdr;       // [G][nloc][8]
   uint32_t *pk_list;     // [G][nloc][V]
@@ -78,3 +81,14 @@ struct PState {
   int mc_tmax;
   int kcap;                     // inbox slots used (P_KMAX - 1; lowered only by the diagnostics env GM_INBOX_CAP)
 };
+
+// host launch wrappers (gm_partial.hip, gm_view_census.hip)
+hipError_t gm_launch_partial_init(const PState &s, int t0, uint64_t init_seed, hipStream_t st);
+hipError_t gm_launch_partial_unpack(const PState &s, int t, int base, int nrecv, hipStream_t st);
+hipError_t gm_launch_partial_pack(const PState &s, int t, int c, hipStream_t st);
+hipError_t gm_launch_partial_mtgen(const PState &s, int t, uint32_t *mtraw, hipStream_t st, bool reset);
+hipError_t gm_launch_partial_reset(const PState &s, hipStream_t st);
+hipError_t gm_launch_partial_chunk(const PState &s, int t, const uint32_t *mtraw, int c, hipStream_t st);
+hipError_t gm_launch_view_census(const PState &s, const uint32_t *cls, void *acc, gm_view_rec *rec, uint64_t *hist,
+                                 uint64_t *sizes, uint32_t *status, int T, hipStream_t st);
+size_t gm_partial_lds_bytes();

@@ -862,7 +862,7 @@ __global__ __launch_bounds__(256) void gm_p_unpack(PState s, int t, int base, in
 // record slots in the tile by LDS atomics, ONE global atomic per (tile, peer) reserves each peer's
 // run (the receivers' merge is order-free), and each node's list is read and converted once, by a
 // half-wave, then written to each of its records. A block that would exceed its capacity (pk_cap,
-// gm_host.hip xcap) sets GM_ERR_XCHG, never drops a record silently.
+// gm_host_partial.hip xcap) sets GM_ERR_XCHG, never drops a record silently.
 template <int VF>
 __global__ __launch_bounds__(256) void gm_p_pack(PState s, int t, int c, int r0, int r1) {
   extern __shared__ int pk_sm[];  // [G] records per peer in this tile, then [G] the tile's run in each block

@@ -3,7 +3,7 @@
 //
 // The stored form is layout-dependent (gm_scaled.h: one byte per cell relative to wtick[r], escaped
 // cells as entries of per-(band, row) lists, inline slot then striped pool); what a caller wants is
-// not: hb / ts per column, -1 = absent (gm_host.hip decode_scaled_row). gm_read_table copies the
+// not: hb / ts per column, -1 = absent (gm_host_read.hip decode_scaled_row). gm_read_table copies the
 // whole stored state to the host and decodes there; here the rows [r0, r0 + rows) are decoded where
 // they live, into a staging block `int32 hb[rows][w]` then `int32 ts[rows][w]` over the context's w
 // real columns (padding columns are not written), and only that block crosses to the host.
@@ -27,8 +27,8 @@
 //                lane is scattered into it by its column, and the lanes take their cells back. A row
 //                piece without an escape byte -- the steady state -- touches neither its record, the
 //                lists nor LDS.
-//                Nothing of a list is trusted before it is checked, as ScaledSnapshot::decode and
-//                place_entries check it on the host: the piece's count of escape bytes equals the
+//                Nothing of a list is trusted before it is checked, as place_esc_list (gm_host_read.hip)
+//                checks it on the host: the piece's count of escape bytes equals the
 //                record's S_EW_TOT, the pool extent lies inside the stripe's region, every entry's
 //                column is < B and names an escape byte -- one still open, so an entry naming a cell
 //                twice, and with it the escape byte left without an entry (which the host decoder

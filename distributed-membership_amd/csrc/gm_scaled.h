@@ -2,6 +2,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "gm_abi.h"
 #include "gm_device.h"
 
 #define S_KMAX 64                // inbox capacity (gossip lists per receiver per tick)
@@ -47,7 +48,7 @@
 // << 11 (0: no escapes), so a reader knows the list's extent with the row's metadata and
 // prefetches the inline entries with the payload gathers; it scatters the entries into its
 // row's cells through LDS (entries carry their columns: no per-cell search). Capacity is
-// bounded (gm_host.hip: dense-equivalent for small clusters, a fraction of the cells beyond);
+// bounded (gm_host_scaled.hip: dense-equivalent for small clusters, a fraction of the cells beyond);
 // an overflow sets GM_ERR_ESC (-> GM_ERANGE) -- never a silent divergence.
 #define S_B_ESC 1u
 #define S_H4_MIN_H 230u  // smallest h a stored byte holds (h4 = 3)
@@ -177,7 +178,7 @@ struct SState {
   int32_t *acc;              // [n][8]: targets so far, g[5], numpot, size
   int32_t *pending;          // [n] rows still drawing
   int32_t *npending;         // rows still drawing after the last accept round
-  // bounded rounds (tick_sharded): pending list l = 1, 2 holds the rows left after round l-1
+  // bounded rounds (gm_host_shard.hip tick_sharded): pending list l = 1, 2 holds the rows left after round l-1
   // (ascending after gm_s_plist_sort: the same order on every rank); statusl[l] = the bound
   // exchange buffer [plist_cap[l]][D_l] of round l's draws, by list position. Index 0 unused.
   int plist_cap[3];
@@ -540,3 +541,30 @@ __device__ __forceinline__ uint32_t unit_stores(const SState &s, int t, const Un
   }
   return eb_out;
 }
+
+// host launch wrappers (gm_scaled.hip; gm_detect.hip, gm_load.hip, gm_census.hip, gm_read.hip)
+hipError_t gm_launch_tick(const SState &s, int t, int drop_pct, hipStream_t st, hipEvent_t k0, hipEvent_t k1,
+                          bool pick);
+hipError_t gm_launch_tick_prologue(const SState &s, int t, hipStream_t st, bool zero_draw = false);
+hipError_t gm_launch_band_rows(const SState &s, int t, int drop_pct, int r0, int r1, hipStream_t st);
+hipError_t gm_launch_xrows(const SState &s, int r0, int r1, hipStream_t st);
+hipError_t gm_launch_draw0(const SState &s, int t, int r0, int r1, hipStream_t st);
+hipError_t gm_launch_draw(const SState &s, int t, int round, int D, int listed, hipStream_t st, int r0 = 0, int r1 = -1);
+hipError_t gm_launch_accept(const SState &s, int t, int D, int in_list, int out, hipStream_t st, int r0 = 0,
+                            int r1 = -1);
+hipError_t gm_launch_plist_sort(const SState &s, int l, hipStream_t st);
+hipError_t gm_launch_init(const SState &s, int warm, int t0, uint64_t seed, hipStream_t st);
+hipError_t gm_launch_msgcount(const SState &s, int t, bool dropped, int phase, hipStream_t st);
+hipError_t gm_launch_detect(const SState &s, gm_detect_rec *rec, uint64_t *timeline, int t, hipStream_t st);
+hipError_t gm_launch_census(const SState &s, gm_census_rec *rec, uint64_t *hist, uint32_t *status, int T,
+                            hipStream_t st);
+hipError_t gm_launch_load_check(const SState &s, int t, int r0, int cnt, const int32_t *hb, const int32_t *ts,
+                                int32_t *base, int32_t *own, uint32_t *status, hipStream_t st);
+hipError_t gm_launch_load_encode(const SState &s, int t, int r0, int cnt, const int32_t *hb, const int32_t *ts,
+                                 const int32_t *base, hipStream_t st);
+hipError_t gm_launch_load_nodes(const SState &s, int t, const int32_t *heartbeat, const int32_t *failed,
+                                const int32_t *targets, const int32_t *counts, const int32_t *own, uint32_t *status,
+                                int write, hipStream_t st);
+hipError_t gm_launch_load_inbox(const SState &s, int t, uint32_t *status, hipStream_t st);
+hipError_t gm_launch_read_decode(const SState &s, int par, int r0, int rows, int32_t *stage, uint32_t *status,
+                                 hipStream_t st);

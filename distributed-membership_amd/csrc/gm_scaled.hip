@@ -2191,7 +2191,7 @@ __global__ __launch_bounds__(256) void gm_s_accept(SState s, int t, int D, int i
     // [16 + 64(q-1), 16 + 64q), so bounded round 1 = host round 1 and bounded round 2 (outputs
     // [80, 336)) = host rounds 2..5. A row no bounded round takes (its list is full, or it is
     // still short after round 2) is counted in npending; the host finishes it with the
-    // host-driven rounds before anything reads the tick (draw_settle, gm_host.hip)
+    // host-driven rounds before anything reads the tick (draw_settle, gm_host_shard.hip)
     if (out == 0) {
       atomicAdd(s.npending, 1);  // gm_s_draw advanced pending[r]
     } else if (out > 0) {
@@ -2284,7 +2284,7 @@ __global__ __launch_bounds__(256) void gm_s_init(SState s, int warm, int t0, uin
 }
 
 // ------------------------------------------------------------ launch wrappers
-// (template dispatch over the band width; called by gm_host.hip)
+// (template dispatch over the band width; called by the gm_host*.hip units)
 // the band kernels of rows [r0, r1) (r0, r1 multiples of the rows per unit, or r1 = n)
 #ifndef GM_FAST_BPW
 #define GM_FAST_BPW 2  // bands per wave of gm_s_band_fast (profiles/r05/ab4, ab5: 3.38 vs 3.48 ms at one)

@@ -3,7 +3,7 @@
 // One pass over the stored views of this context's live observers: per subject node of the cluster
 // one gm_view_rec (holders, stale entries, heartbeat range and sum), the histogram of the entries
 // by (subject's crash flag, age) and the histogram of the view sizes. The views stay on the device;
-// 24 n bytes plus the two histograms go back (gm_host.hip gm_view_census). Nothing the tick kernels
+// 24 n bytes plus the two histograms go back (gm_host_read.hip gm_view_census). Nothing the tick kernels
 // read is written: the reducer's only outputs are its own scratch.
 //
 // An entry's timestamp is derived from its heartbeat (ts = (hb + 1) / 2, gm_partial.hip), so its age

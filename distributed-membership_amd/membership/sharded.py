@@ -22,7 +22,7 @@ import os
 
 from .abi import GM_MODE_SCALED, Simulator, comm_unique_id, shard_loopback
 
-D_FIRST = 16        # must match GM_D_FIRST in gm_host.hip
+D_FIRST = 16        # must match GM_D_FIRST in gm_host.h
 D_MORE = 64         # must match GM_D_MORE
 MAX_ROUNDS = 4096   # must match GM_MAX_ROUNDS: a row that never fills its targets
 

@@ -13,7 +13,7 @@ for spec in "$@"; do
   name=${spec%%:*}; flags=${spec#*:}
   mkdir -p build_var/$name
   /opt/rocm/bin/hipcc $HIPFLAGS $flags -c -o build_var/$name/gm_partial.o $C/gm_partial.hip
-  /opt/rocm/bin/hipcc $HIPFLAGS -shared -o build_var/$name/libgm.so $B/gm_faithful.o $B/gm_scaled.o \
-    build_var/$name/gm_partial.o $B/gm_host.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+  /opt/rocm/bin/hipcc $HIPFLAGS -shared -o build_var/$name/libgm.so build_var/$name/gm_partial.o \
+    $(ls $B/*.o | grep -v /gm_partial.o) -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
   echo "built build_var/$name/libgm.so ($flags)"
 done

@@ -2,6 +2,8 @@
 entry points include/gm_abi.h declares; the host-only helpers agree with the oracle."""
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -25,6 +27,17 @@ def test_library_exports_all_symbols():
     lib = abi.load_library()
     for name in declared():
         assert hasattr(lib, name), name
+
+
+def test_library_exports_nothing_else():
+    # the other direction: every defined dynamic symbol named gm_* without C++ mangling is declared
+    nm = shutil.which("nm")
+    if nm is None:
+        pytest.skip("nm (binutils) is not installed")
+    abi.load_library()  # raises when the library is not built
+    out = subprocess.run([nm, "-D", "--defined-only", abi.lib_path()], check=True, capture_output=True, text=True).stdout
+    exported = sorted({line.split()[-1].split("@")[0] for line in out.splitlines() if line.split()[-1].startswith("gm_")})
+    assert exported == declared()
 
 
 def test_product_is_built_for_gfx950():

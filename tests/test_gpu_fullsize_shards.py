@@ -68,7 +68,7 @@ def test_sb_full_size_column_shards_match_single_context(sb_single_context, path
     separate calls). pipelined: gm_shard_loopback_tick, the production tick's order -- the band
     kernels in K = 2 exchange chunks on the compute stream, each chunk's row totals, all-gather,
     draw round 0 (gm_s_draw0), MAX-allreduce and acceptance behind them, then the bounded rounds
-    (gm_host.hip tick_sharded; the collectives by device copies). VERDICT r5 weak 5 / next 2.
+    (gm_host_shard.hip tick_sharded; the collectives by device copies). VERDICT r5 weak 5 / next 2.
     Reference: the BSP tick Application.cpp:121-164."""
     n = SB_N
     ncrash, crash, crashed, rows = _sb_crash()

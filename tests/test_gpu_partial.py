@@ -143,7 +143,7 @@ def test_rccl_single_rank_row_shard_matches_oracle(monkeypatch):
 
 
 def block_caps(n, world, chunks, failed):
-    """Python mirror of gm_host.hip xcap: capacity of every (sender shard g, chunk c, receiver q)
+    """Python mirror of gm_host_partial.hip xcap: capacity of every (sender shard g, chunk c, receiver q)
     block from the live nodes per shard -- f_q = max(n_q / n, live_q / live), address probability
     p = 1 - (1 - f_q)^5, capacity min(rows, ceil(rows p + 8 sqrt(rows p (1 - p)) + 64))."""
     import math

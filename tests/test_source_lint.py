@@ -1,7 +1,7 @@
 """CPU lint over the product sources (csrc/, app/).
 
 Every copy and fill of a context must go through the context's own non-blocking stream
-(`ctx_memset` / `ctx_memcpy` / `ctx_memcpy2d`, gm_host.hip): a synchronous null-stream call
+(`ctx_memset` / `ctx_memcpy` / `ctx_memcpy2d`, gm_host.h): a synchronous null-stream call
 (`hipMemset`, `hipMemcpy`, `hipMemcpy2D`, the symbol copies) is not ordered against the
 context's kernels. One such fill at creation raced `gm_p_init` and zeroed S-C rows
 (intermittent GM_ERR_SELF in rounds r04u / r04z, profiles/r04/sc_self_flake/README.md).
