@@ -10,13 +10,16 @@ PKG := distributed-membership_amd
 CSRC := $(PKG)/csrc
 HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -I$(CSRC) -Wall -Wno-unused-result
 LIB := $(PKG)/lib/libgm.so
-KOBJS := $(PKG)/build/gm_faithful.o $(PKG)/build/gm_scaled.o $(PKG)/build/gm_partial.o $(PKG)/build/gm_detect.o \
+KOBJS := $(PKG)/build/gm_faithful.o $(PKG)/build/gm_scaled.o $(PKG)/build/gm_band.o $(PKG)/build/gm_draw.o \
+         $(PKG)/build/gm_partial.o $(PKG)/build/gm_detect.o \
          $(PKG)/build/gm_load.o $(PKG)/build/gm_census.o $(PKG)/build/gm_view_census.o $(PKG)/build/gm_read.o \
          $(PKG)/build/gm_host.o $(PKG)/build/gm_host_faithful.o $(PKG)/build/gm_host_scaled.o \
          $(PKG)/build/gm_host_shard.o $(PKG)/build/gm_host_partial.o $(PKG)/build/gm_host_events.o \
          $(PKG)/build/gm_host_read.o $(PKG)/build/gm_host_load.o
 HDRS := include/gm_abi.h $(CSRC)/gm_device.h $(CSRC)/gm_faithful.h $(CSRC)/gm_scaled.h $(CSRC)/gm_partial.h \
-        $(CSRC)/gm_host.h
+        $(CSRC)/gm_host.h $(CSRC)/gm_band.h $(CSRC)/gm_select.h
+# kernel files compiled as part of another unit (gm_band.hip, gm_draw.hip include them)
+HDRS += $(CSRC)/gm_band_fast.hip $(CSRC)/gm_pick.hip
 
 all: $(LIB) Application oracle
 

@@ -1,4 +1,4 @@
-// gm_host_scaled.hip -- SCALED host side: sizing and allocation of gm_scaled.hip's state, and the
+// gm_host_scaled.hip -- SCALED host side: sizing and allocation of the SCALED kernels' state (gm_scaled.h), and the
 // tick of a single context (a column shard's tick is gm_host_shard.hip's).
 #include "gm_host.h"
 
@@ -8,7 +8,7 @@ using namespace gmh;
 // the padded row) whose per-band traffic -- N rows x band x (2 B cell read + 2 B
 // write + 1 B payload write + 1 B payload read) -- stays within ~210 MB, so a band's
 // payload slab stays resident in the 256 MiB Infinity Cache across its ~5 readers
-// per sender slice (gm_scaled.hip). gm_config.band / env GM_BAND override.
+// per sender slice (gm_band.h). gm_config.band / env GM_BAND override.
 static int pick_band(const gm_ctx *c, int n, int wp) {
   int b = c->cfg.band;
   if (!b && getenv("GM_BAND")) b = atoi(getenv("GM_BAND"));

@@ -208,15 +208,10 @@ static void launch_encode_b(const SState &s, int t, int r0, int cnt, const int32
 
 hipError_t gm_launch_load_encode(const SState &s, int t, int r0, int cnt, const int32_t *hb, const int32_t *ts,
                                  const int32_t *base, hipStream_t st) {
-  switch (s.band) {
-    case 64: launch_encode_b<64>(s, t, r0, cnt, hb, ts, base, st); break;
-    case 128: launch_encode_b<128>(s, t, r0, cnt, hb, ts, base, st); break;
-    case 256: launch_encode_b<256>(s, t, r0, cnt, hb, ts, base, st); break;
-    case 512: launch_encode_b<512>(s, t, r0, cnt, hb, ts, base, st); break;
-    case 1024: launch_encode_b<1024>(s, t, r0, cnt, hb, ts, base, st); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return gm_band_dispatch(s.band, [&](auto b) {
+    launch_encode_b<decltype(b)::value>(s, t, r0, cnt, hb, ts, base, st);
+    return hipGetLastError();
+  });
 }
 
 hipError_t gm_launch_load_nodes(const SState &s, int t, const int32_t *heartbeat, const int32_t *failed,

@@ -174,13 +174,8 @@ static void launch_decode_b(const SState &s, int par, int r0, int rows, int32_t 
 hipError_t gm_launch_read_decode(const SState &s, int par, int r0, int rows, int32_t *stage, uint32_t *status,
                                  hipStream_t st) {
   if (rows <= 0 || r0 < 0 || r0 + (int64_t)rows > s.n) return hipErrorInvalidValue;
-  switch (s.band) {
-    case 64: launch_decode_b<64>(s, par, r0, rows, stage, status, st); break;
-    case 128: launch_decode_b<128>(s, par, r0, rows, stage, status, st); break;
-    case 256: launch_decode_b<256>(s, par, r0, rows, stage, status, st); break;
-    case 512: launch_decode_b<512>(s, par, r0, rows, stage, status, st); break;
-    case 1024: launch_decode_b<1024>(s, par, r0, rows, stage, status, st); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return gm_band_dispatch(s.band, [&](auto b) {
+    launch_decode_b<decltype(b)::value>(s, par, r0, rows, stage, status, st);
+    return hipGetLastError();
+  });
 }

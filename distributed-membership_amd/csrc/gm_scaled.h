@@ -1,6 +1,11 @@
-// gm_scaled.h -- device state of the SCALED tick (see gm_scaled.hip).
+// gm_scaled.h -- device state of the SCALED tick, the cell encoding, the store side of the band
+// sweep and the host launch wrappers. The kernels are in units by concern: gm_scaled.hip (overview;
+// gm_s_mtgen, init, msgcount, gm_launch_tick), gm_band.hip / gm_band_fast.hip (the band sweep),
+// gm_pick.hip (the single-context draw), gm_draw.hip (the column-shard draw protocol).
 #pragma once
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "gm_abi.h"
 #include "gm_device.h"
@@ -89,7 +94,7 @@ __host__ __device__ inline bool s_ingroup(int ramp, int intro_until, int r, int 
 #define S_NIB_ESC 15u
 #define S_NIB_H(n) (S_NIB_BASE + 2u * (n))
 
-// keyed loss threshold (gm_device.h gm_drop_thresh; gm_scaled.hip s_keep)
+// keyed loss threshold (gm_device.h gm_drop_thresh; gm_band.h s_keep)
 __host__ __device__ inline uint32_t s_drop_thresh(int pct) { return gm_drop_thresh(pct); }
 
 // status word of a state-loading call's device checks (gm_load.hip)
@@ -213,7 +218,7 @@ struct SState {
 
 // ------------------------------------------------------------------ device helpers
 // The store side of the band sweep (narrowing, escape lists, payload nibbles and escape slots),
-// shared by the tick kernels (gm_scaled.hip) and the state loader's encode kernel (gm_load.hip):
+// shared by the band kernels (gm_band.h) and the state loader's encode kernel (gm_load.hip):
 // one encoder of the stored form.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
@@ -263,13 +268,18 @@ __device__ __forceinline__ u16x2 widen2(u16x2 x, u16x2 nz) {
   return nz * (u16x2)(7168) + ((x & (u16x2)(0xF0)) * (u16x2)(3) + x);
 }
 
-// wave-wide inclusive scan on DPP: row_shr 1/2/4/8 within each 16-lane row, row_bcast15 /
-// row_bcast31 carry the row totals upward (lanes a DPP source does not reach add 0)
-__device__ __forceinline__ int dpp_scan(int v) {
+// inclusive scan within each 16-lane DPP row: row_shr 1/2/4/8 (lanes a DPP source does not reach add 0)
+__device__ __forceinline__ int row16_scan(int v) {
   v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);  // row_shr:1
   v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);  // row_shr:2
   v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);  // row_shr:4
   v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);  // row_shr:8
+  return v;
+}
+// wave-wide inclusive scan on DPP: the rows' scans, then row_bcast15 / row_bcast31 carry the row
+// totals upward
+__device__ __forceinline__ int dpp_scan(int v) {
+  v = row16_scan(v);
   v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
   v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
   return v;
@@ -542,7 +552,23 @@ __device__ __forceinline__ uint32_t unit_stores(const SState &s, int t, const Un
   return eb_out;
 }
 
-// host launch wrappers (gm_scaled.hip; gm_detect.hip, gm_load.hip, gm_census.hip, gm_read.hip)
+// The band width as a compile-time constant: calls f(std::integral_constant<int, B>{}) for band = B
+// and returns its hipError_t; hipErrorInvalidValue for a width no kernel is instantiated at.
+template <typename F>
+inline hipError_t gm_band_dispatch(int band, F &&f) {
+  switch (band) {
+    case 64: return f(std::integral_constant<int, 64>{});
+    case 128: return f(std::integral_constant<int, 128>{});
+    case 256: return f(std::integral_constant<int, 256>{});
+    case 512: return f(std::integral_constant<int, 512>{});
+    case 1024: return f(std::integral_constant<int, 1024>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// host launch wrappers, for the gm_host*.hip units (gm_scaled.hip, gm_band.hip, gm_draw.hip; gm_detect.hip,
+// gm_load.hip, gm_census.hip, gm_read.hip). Launchers only another SCALED kernel unit calls are
+// declared in gm_band.h / gm_select.h.
 hipError_t gm_launch_tick(const SState &s, int t, int drop_pct, hipStream_t st, hipEvent_t k0, hipEvent_t k1,
                           bool pick);
 hipError_t gm_launch_tick_prologue(const SState &s, int t, hipStream_t st, bool zero_draw = false);

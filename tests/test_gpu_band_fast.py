@@ -1,5 +1,5 @@
 """gm_s_band's fast path (B = 1024: merge and sweep on the stored bytes, SWAR counts, the rare
-cells redone one by one; gm_scaled.hip unit_fast) against the general path (GM_BAND_FAST=0),
+cells redone one by one; gm_band_fast.hip unit_fast) against the general path (GM_BAND_FAST=0),
 tick by tick: events in order, tick statistics, membership tables, msgcount. The schedules drive
 every branch of the fast path: the crash window (cells aging to 15 escape, then TREMOVE removes
 them: the per-cell pass, the quick case of a slice whose escapes only age, and the removal events), cold start (every cell escaped: escape lists read

@@ -1,4 +1,4 @@
-"""gm_s_band_fast's row order (gm_scaled.hip: the grid's x interleaves GM_FAST_XS stripes of
+"""gm_s_band_fast's row order (gm_band_fast.hip: the grid's x interleaves GM_FAST_XS stripes of
 consecutive rows) and its plain, single-writer evcum write against the general path
 (GM_BAND_FAST=0), tick by tick, at band 1024.
 
