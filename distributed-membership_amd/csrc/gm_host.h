@@ -8,7 +8,7 @@
 //   gm_host_partial.hip   PARTIAL: state, tick, the row shards' exchange
 //   gm_host_events.hip    event drains, detection recorder, msgcount
 //   gm_host_read.hip      read-backs: rows, tables, views, nodes, targets, the censuses
-//   gm_host_load.hip      gm_load_*
+//   gm_host_load.hip      gm_load_*, gm_load_views_*
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -78,6 +78,26 @@ struct gm_load_stage {
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
 };
 
+// PARTIAL view loading (gm_load_views_begin .. gm_load_views_commit). One device block (blob, at most
+// 256 MiB, freed by the commit): the staged views of up to cap nodes -- the commit stages the node
+// arrays through the same rows, ncap nodes at a time --, the "given" bitmap of this context's nodes,
+// the status word of a call's checks.
+struct gm_view_load_stage {
+  bool loading = false;              // between gm_load_views_begin and a successful gm_load_views_commit
+  bool voided = false;               // a load call failed: only gm_load_views_begin starts over
+  bool xpending = false;             // row shards: committed, the exchange of tick t - 1 is replayed by the next tick
+  int t = 0;                         // gm_load_views_begin's t
+  int cap = 0, ncap = 0;             // staged views per launch; staged nodes per launch of the commit
+  void *blob = nullptr;
+  size_t bytes = 0;
+  uint64_t *rows = nullptr;          // [cap][V]
+  uint32_t *given = nullptr, *status = nullptr;
+  std::vector<uint8_t> seen;         // this context's nodes given so far
+  int64_t nrows = 0;
+  double ms[2] = {0, 0};             // gm_set_timing on: ms in gm_pl_check / gm_pl_store since the begin
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+};
+
 // SCALED rows decoded on the device (gm_read_rows): one device block, allocated by the first call and
 // reused -- the staging planes hb, ts [cap][w] of one decode launch, then the kernel's status word
 struct gm_read_stage {
@@ -107,7 +127,7 @@ struct gm_partial_host {
   std::vector<double> xq;            // per row shard q: probability that a sender addresses q (xcap)
   uint64_t crash_hash = 0;           // hash of the whole crash set the block capacities were derived from
   bool crash_check = false;          // agree it across the ranks at the next RCCL tick
-  uint64_t *crash_dev = nullptr;     // [2] device words of that check
+  uint64_t *crash_dev = nullptr;     // [4] device words of that check (the hash, the "exchange pending" flag)
 };
 
 // The chunk-pipelined exchange of a sharded tick, SCALED column shards and PARTIAL row shards alike:
@@ -166,6 +186,7 @@ struct gm_ctx {
   PState p{};  // PARTIAL
   gm_partial_host ph;
   gm_view_census_scratch vc;
+  gm_view_load_stage vl;
   gm_shard_exchange xch;  // SCALED column shards, PARTIAL row shards
 };
 
@@ -286,6 +307,7 @@ int before_tick_events(gm_ctx *c);
 
 // gm_host_load.hip, gm_host_read.hip
 void load_destroy(gm_ctx *c);
+void vload_destroy(gm_ctx *c);
 void read_destroy(gm_ctx *c);
 
 }  // namespace gmh

@@ -118,6 +118,7 @@ extern "C" int gm_destroy(gm_ctx *c) {
   if (c->comm) (void)ncclCommDestroy(c->comm);
   for (void *p : c->allocs) (void)hipFree(p);
   load_destroy(c);
+  vload_destroy(c);
   read_destroy(c);
   destroy_scaled(c);
   destroy_faithful(c);
@@ -207,7 +208,7 @@ void gmh::advance(gm_ctx *c) {  // a tick was enqueued: globaltime moves on
 extern "C" int gm_tick(gm_ctx *c) {
   if (!c) return GM_EINVAL;
   if (c->latched != GM_OK) return c->latched;
-  if (c->ld.loading) return GM_ESTATE;  // between gm_load_begin and gm_load_commit
+  if (c->ld.loading || c->vl.loading) return GM_ESTATE;  // between gm_load_begin / gm_load_views_begin and the commit
   if (c->cfg.mode == GM_MODE_SCALED) TRY(draw_settle(&c, 1));
   TRY(before_tick_events(c));
   int rc = c->cfg.mode == GM_MODE_FAITHFUL ? tick_faithful(c) : c->cfg.mode == GM_MODE_SCALED ? tick_scaled(c)
@@ -250,7 +251,7 @@ extern "C" int gm_set_failed(gm_ctx *c, const int32_t *idx, int32_t n) {
   if (!c || n < 0 || (n > 0 && !idx)) return GM_EINVAL;
   for (int k = 0; k < n; k++)  // validate everything before any state changes
     if (idx[k] < 0 || idx[k] >= c->n) return GM_EINVAL;
-  if (c->ld.loading) return GM_ESTATE;  // the commit sets the crash flags
+  if (c->ld.loading || c->vl.loading) return GM_ESTATE;  // the commit sets the crash flags
   TRY(f_settle(c));
   for (int k = 0; k < n; k++) {
     c->nfailed += c->failed_h[idx[k]] == 0;

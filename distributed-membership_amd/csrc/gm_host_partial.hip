@@ -201,22 +201,27 @@ int gmh::partial_caps(gm_ctx *c) {
 // differently and hang or corrupt it. After each change the group agrees on the set's hash -- an RCCL
 // rank by one MAX-allreduce of (h, ~h), a loopback group on the host -- and any disagreement latches
 // GM_ESTATE on every member.
+// A loaded view state (gm_load_views_commit) rides along: its commit changes the crash set's hash
+// check too, and the "exchange pending" flag of every member must agree -- the replayed exchange of
+// tick t - 1 is a collective like any other. RCCL ranks carry the flag as words 2, 3 of the all-reduce.
 static int px_agree(gm_ctx **g, int G, hipStream_t st) {
   bool same = true;
   if (G == 1) {
     gm_ctx *c = g[0];
     if (!c->ph.crash_dev) {
-      HIPCHECK(hipMalloc(&c->ph.crash_dev, 2 * sizeof(uint64_t)));
+      HIPCHECK(hipMalloc(&c->ph.crash_dev, 4 * sizeof(uint64_t)));
       c->allocs.push_back(c->ph.crash_dev);
     }
-    uint64_t hv[2] = {c->ph.crash_hash, ~c->ph.crash_hash}, mx[2] = {0, 0};
+    const uint64_t pend = c->vl.xpending ? 1 : 0;
+    uint64_t hv[4] = {c->ph.crash_hash, ~c->ph.crash_hash, pend, ~pend}, mx[4] = {0, 0, 0, 0};
     HIPCHECK(hipMemcpyAsync(c->ph.crash_dev, hv, sizeof hv, hipMemcpyHostToDevice, st));
-    NCCLCHECK(ncclAllReduce(c->ph.crash_dev, c->ph.crash_dev, 2, ncclUint64, ncclMax, c->comm, st));
+    NCCLCHECK(ncclAllReduce(c->ph.crash_dev, c->ph.crash_dev, 4, ncclUint64, ncclMax, c->comm, st));
     HIPCHECK(hipMemcpyAsync(mx, c->ph.crash_dev, sizeof mx, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
-    same = mx[0] == hv[0] && mx[1] == hv[1];
+    same = mx[0] == hv[0] && mx[1] == hv[1] && mx[2] == hv[2] && mx[3] == hv[3];
   }
-  for (int i = 1; i < G; i++) same &= g[i]->ph.crash_hash == g[0]->ph.crash_hash;
+  for (int i = 1; i < G; i++)
+    same &= g[i]->ph.crash_hash == g[0]->ph.crash_hash && g[i]->vl.xpending == g[0]->vl.xpending;
   for (int i = 0; i < G && !same; i++) g[i]->latched = GM_ESTATE;
   return same ? GM_OK : GM_ESTATE;
 }
@@ -224,8 +229,10 @@ static int px_agree(gm_ctx **g, int G, hipStream_t st) {
 // The exchange of chunk ch on the comm stream: every member packs, then each member receives its
 // blocks -- two ncclAllToAllv for an RCCL rank, device copies from its peers' packed blocks in a
 // loopback group (same layout; both sides must have sized the block alike) -- and unpacks them.
-static int px_exchange(gm_ctx **g, int G, int ch, hipStream_t cs) {
-  const int t = g[0]->t, V = g[0]->p.V;
+// t: the tick whose sends travel -- the group's current tick, or the tick before it when a loaded
+// state's exchange is replayed.
+static int px_exchange(gm_ctx **g, int G, int ch, hipStream_t cs, int t) {
+  const int V = g[0]->p.V;
   for (int i = 0; i < G; i++) {
     const PState &p = g[i]->p;
     if (ch == 0) HIPCHECK(hipMemsetAsync(p.pk_cnt, 0, sizeof(int32_t) * p.nchunk * p.G, cs));
@@ -305,7 +312,20 @@ int gmh::tick_partial(gm_ctx **g, int G) {
       check |= g[i]->ph.crash_check;
       g[i]->ph.crash_check = false;
     }
-    if (check) TRY(px_agree(g, G, st));
+    bool pend = false;
+    for (int i = 0; i < G; i++) pend |= g[i]->vl.xpending;
+    if (check || pend) TRY(px_agree(g, G, st));  // (a commit always asks for the check: partial_caps)
+    if (pend) {
+      // a loaded state: the received lists and the remote half of the inboxes of tick t are what
+      // tick t - 1's exchange delivered. Replay it from what the commit wrote -- targets,
+      // rowstat[.][3], lists[(t - 1) & 1] -- for all K chunks on the comm stream, before this tick's work
+      HIPCHECK(hipEventRecord(L->xch.done, st));
+      HIPCHECK(hipStreamWaitEvent(L->xch.stream, L->xch.done, 0));
+      for (int q = 0; q < K; q++) TRY(px_exchange(g, G, q, L->xch.stream, t - 1));
+      HIPCHECK(hipEventRecord(L->xch.done, L->xch.stream));
+      HIPCHECK(hipStreamWaitEvent(st, L->xch.done, 0));
+      for (int i = 0; i < G; i++) g[i]->vl.xpending = false;
+    }
     // chunk pipeline: every chunk's node ticks queue on the compute stream; the exchange of
     // chunk q runs on the comm stream once q's kernels are done, while q+1.. still compute
     for (int q = 0; q < K; q++) {
@@ -315,7 +335,7 @@ int gmh::tick_partial(gm_ctx **g, int G) {
     if (k1) HIPCHECK(hipEventRecord(k1, st));
     for (int q = 0; q < K; q++) {
       HIPCHECK(hipStreamWaitEvent(L->xch.stream, L->xch.chunk_ev[q], 0));
-      TRY(px_exchange(g, G, q, L->xch.stream));
+      TRY(px_exchange(g, G, q, L->xch.stream, t));
     }
     HIPCHECK(hipEventRecord(L->xch.done, L->xch.stream));
     HIPCHECK(hipStreamWaitEvent(st, L->xch.done, 0));  // the next tick reads the unpacked inboxes
@@ -347,6 +367,7 @@ extern "C" int gm_partial_loopback_tick(gm_ctx **ctxs, int32_t G) {
         c->n != ctxs[0]->n || c->p.V != ctxs[0]->p.V || c->p.nchunk != ctxs[0]->p.nchunk)
       return GM_EINVAL;
     if (c->latched != GM_OK) return c->latched;
+    if (c->vl.loading) return GM_ESTATE;  // between gm_load_views_begin and gm_load_views_commit
   }
   for (int g = 0; g < G; g++) TRY(before_tick_events(ctxs[g]));
   for (int g = 0; g < G; g++) HIPCHECK(hipStreamSynchronize(ctxs[g]->stream));  // the tick runs on the first member's streams

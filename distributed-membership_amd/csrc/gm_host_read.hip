@@ -379,6 +379,19 @@ extern "C" int gm_dump_tables(gm_ctx *c, char *buf, size_t cap, size_t *len) {
 
 extern "C" int gm_read_targets(gm_ctx *c, int32_t *targets, int32_t *counts) {
   if (!c || !targets || !counts) return GM_EINVAL;
+  if (c->cfg.mode == GM_MODE_PARTIAL) {  // this context's own nodes: [nloc][5] global indices, counts [nloc]
+    const size_t nl = (size_t)c->p.nloc;
+    std::vector<int32_t> st(nl * 4);
+    if (c->xch.stream) HIPCHECK(hipStreamSynchronize(c->xch.stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    HIPCHECK(ctx_memcpy(c, targets, c->p.targets, sizeof(int32_t) * nl * GM_FANOUT, hipMemcpyDeviceToHost));
+    HIPCHECK(ctx_memcpy(c, st.data(), c->p.rowstat, sizeof(int32_t) * nl * 4, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < nl; r++) {
+      counts[r] = st[r * 4 + 3];
+      for (int q = counts[r]; q < GM_FANOUT; q++) targets[r * GM_FANOUT + q] = 0;
+    }
+    return check_err(c);
+  }
   if (c->cfg.mode != GM_MODE_SCALED) return GM_EUNSUPPORTED;
   TRY(draw_settle(&c, 1));
   const size_t n = (size_t)c->n;

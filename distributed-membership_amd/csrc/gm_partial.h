@@ -82,7 +82,25 @@ struct PState {
   int kcap;                     // inbox slots used (P_KMAX - 1; lowered only by the diagnostics env GM_INBOX_CAP)
 };
 
-// host launch wrappers (gm_partial.hip, gm_view_census.hip)
+// status word of the view-load kernels (gm_load_views.hip): what a loaded state violates. The low 16 bits
+// are malformed input (GM_EINVAL), the high ones a bounded resource (GM_ERANGE)
+#define GM_PL_EID 0x1u         // an id outside [1, n]
+#define GM_PL_EORDER 0x2u      // ids not strictly ascending
+#define GM_PL_EGAP 0x4u        // an entry after an empty slot
+#define GM_PL_EHBPAR 0x8u      // an even heartbeat
+#define GM_PL_EHBTOP 0x10u     // a heartbeat above 2(t - 1) - 1
+#define GM_PL_EAGE 0x20u       // a live node's entry aged GM_VIEW_AGES or more
+#define GM_PL_ESELF 0x40u      // the node's own entry missing, or not {heartbeat - 1}
+#define GM_PL_EHEARTBEAT 0x80u // live: heartbeat != 2(t - 1); crashed: odd or above it
+#define GM_PL_EFAILED 0x100u   // a crash flag that is not 0 / 1
+#define GM_PL_ECOUNT 0x200u    // a count outside 0..5
+#define GM_PL_ETARGET 0x400u   // a target outside [0, n), the node itself, named twice, or not in its view
+#define GM_PL_ECRASHED 0x800u  // a crashed node with targets that did not run tick t - 1
+#define GM_PL_EMISSING 0x1000u // a node whose view was not given
+#define GM_PL_EINVAL_MASK 0xFFFFu
+#define GM_PL_EINBOX 0x10000u  // more lists for one receiver than its inbox holds
+
+// host launch wrappers (gm_partial.hip, gm_view_census.hip, gm_load_views.hip)
 hipError_t gm_launch_partial_init(const PState &s, int t0, uint64_t init_seed, hipStream_t st);
 hipError_t gm_launch_partial_unpack(const PState &s, int t, int base, int nrecv, hipStream_t st);
 hipError_t gm_launch_partial_pack(const PState &s, int t, int c, hipStream_t st);
@@ -91,4 +109,12 @@ hipError_t gm_launch_partial_reset(const PState &s, hipStream_t st);
 hipError_t gm_launch_partial_chunk(const PState &s, int t, const uint32_t *mtraw, int c, hipStream_t st);
 hipError_t gm_launch_view_census(const PState &s, const uint32_t *cls, void *acc, gm_view_rec *rec, uint64_t *hist,
                                  uint64_t *sizes, uint32_t *status, int T, hipStream_t st);
+hipError_t gm_launch_view_load_check(const PState &s, int t, int cnt, const uint64_t *stage, uint32_t *status,
+                                     hipStream_t st);
+hipError_t gm_launch_view_load_store(const PState &s, int t, int r0, int cnt, const uint64_t *stage, uint32_t *given,
+                                     hipStream_t st);
+hipError_t gm_launch_view_load_nodes(const PState &s, int t, int r0, int cnt, const int32_t *heartbeat,
+                                     const int32_t *failed, const int32_t *counts, const int32_t *targets,
+                                     const uint32_t *given, uint32_t *status, int write, hipStream_t st);
+hipError_t gm_launch_view_load_inbox(const PState &s, int t, uint32_t *status, hipStream_t st);
 size_t gm_partial_lds_bytes();

@@ -75,7 +75,8 @@ EXPORTS = ["gm_detect_record", "gm_detect", "gm_detect_timeline", "gm_parse_conf
            "gm_shard_exchange_bytes", "gm_keep_events", "gm_event_totals", "gm_read_views", "gm_shard_stub",
            "gm_msgcount_record", "gm_comm_info", "gm_shard_export", "gm_shard_import", "gm_pool_info", "gm_shard_loopback_tick", "gm_read_targets",
            "gm_load_begin", "gm_load_rows", "gm_load_commit", "gm_load_stats", "gm_census", "gm_view_census",
-           "gm_read_rows", "gm_read_rows_stats"]
+           "gm_read_rows", "gm_read_rows_stats",
+           "gm_load_views_begin", "gm_load_views", "gm_load_views_commit", "gm_load_views_stats"]
 
 _lib = None
 
@@ -135,6 +136,9 @@ def load_library():
         "gm_view_census": [ctypes.c_void_p, P(GmViewRec), P(u64), P(u64)],
         "gm_read_rows": [ctypes.c_void_p, i32, i32, P(i32), P(i32)],
         "gm_read_rows_stats": [ctypes.c_void_p, P(ctypes.c_double)],
+        "gm_load_views_begin": [ctypes.c_void_p, i32], "gm_load_views": [ctypes.c_void_p, i32, i32, P(u64)],
+        "gm_load_views_commit": [ctypes.c_void_p, P(i32), P(i32), P(i32), P(i32)],
+        "gm_load_views_stats": [ctypes.c_void_p, P(ctypes.c_double)],
     }
     # GM_AB_BUILD=1 (A/B scripts only): an older measurement build may lack newer entry points, which
     # are then left unbound. Otherwise every entry point must be present, whatever library GM_LIBRARY
@@ -395,9 +399,11 @@ class Simulator:
         return st
 
     def read_targets(self):
-        """SCALED: (targets int32 [n][5], counts int32 [n]) of the last tick (gm_read_targets)"""
-        tg = np.zeros((self.n, 5), dtype=np.int32)
-        cnt = np.zeros(self.n, dtype=np.int32)
+        """SCALED: (targets int32 [n][5], counts int32 [n]) of the last tick (gm_read_targets).
+        PARTIAL: the same for this context's own nodes, [nloc][5] global node indices and [nloc]."""
+        rows = self.shard_layout()[1] if self.mode == GM_MODE_PARTIAL else self.n
+        tg = np.zeros((rows, 5), dtype=np.int32)
+        cnt = np.zeros(rows, dtype=np.int32)
         self._call("gm_read_targets", self.h, _ptr(tg), _ptr(cnt))
         return tg, cnt
 
@@ -429,6 +435,38 @@ class Simulator:
         v = (ctypes.c_double * 4)()
         self._call("gm_load_stats", self.h, v)
         return {"rows": int(v[0]), "staging_bytes": int(v[1]), "check_ms": float(v[2]), "encode_ms": float(v[3])}
+
+    def load_views(self, t, views, heartbeat, failed, targets, counts, chunk_rows=None):
+        """PARTIAL: replace the whole state between two ticks (gm_load_views_begin / gm_load_views /
+        gm_load_views_commit). views uint64 [nloc][V] as read_views returns them for this context's
+        own nodes; heartbeat [nloc]; failed [n], the crash flags of the WHOLE cluster; targets
+        [nloc][5] and counts [nloc] as read_targets returns them; t is the next tick to run. The
+        views go to the device in blocks of chunk_rows nodes (default: about 64 MiB)."""
+        i32 = np.int32
+        n0, nloc = self.shard_layout()
+        v = self.cfg.view or 32
+        vw = np.ascontiguousarray(views, dtype=np.uint64)  # a view of a memory-mapped array: read block by block
+        if vw.shape != (nloc, v):
+            raise ValueError(f"load_views: views of shape {vw.shape}, this context holds [{nloc}][{v}]")
+        hbt = np.ascontiguousarray(heartbeat, dtype=i32).reshape(nloc)
+        fl = np.ascontiguousarray(failed, dtype=i32).reshape(self.n)
+        tg = np.ascontiguousarray(targets, dtype=i32).reshape(nloc, 5)
+        cnt = np.ascontiguousarray(counts, dtype=i32).reshape(nloc)
+        if chunk_rows is None:
+            chunk_rows = max(1, (64 << 20) // (8 * v))
+        self._call("gm_load_views_begin", self.h, int(t))
+        for r0 in range(0, nloc, chunk_rows):
+            m = min(chunk_rows, nloc - r0)
+            blk = np.ascontiguousarray(vw[r0:r0 + m], dtype=np.uint64)
+            self._call("gm_load_views", self.h, n0 + r0, m, _ptr(blk, ctypes.c_uint64))
+        self._call("gm_load_views_commit", self.h, _ptr(hbt), _ptr(fl), _ptr(tg), _ptr(cnt))
+
+    def load_views_stats(self):
+        """{"rows", "staging_bytes", "check_ms", "store_ms"} of the last view load (kernel times only
+        while set_timing is on)"""
+        v = (ctypes.c_double * 4)()
+        self._call("gm_load_views_stats", self.h, v)
+        return {"rows": int(v[0]), "staging_bytes": int(v[1]), "check_ms": float(v[2]), "store_ms": float(v[3])}
 
     def dump_tables(self):
         n = ctypes.c_size_t()

@@ -136,3 +136,131 @@ def join_columns(snaps):
     c0 = np.cumsum([0] + [s["hb"].shape[1] for s in snaps])
     out["heartbeat"] = np.concatenate([s["heartbeat"][c0[g]:c0[g + 1]] for g, s in enumerate(snaps)])
     return out
+
+
+# ---------------------------------------------------------------------------- PARTIAL view states
+# A view snapshot is a dict of
+#   t          the next tick to run
+#   n0         the first node the snapshot covers (a row shard's n0; 0 for a cluster snapshot)
+#   views      uint64 [nloc][V]: the nodes' final views of tick t - 1 (read_views: id << 32 | hb, 0 = empty)
+#   heartbeat  int32 [nloc];  failed int32 [n]: the crash flags of the WHOLE cluster, in every snapshot
+#   targets    int32 [nloc][5], counts int32 [nloc]: the targets drawn in tick t - 1 (read_targets)
+# which is everything gm_load_views_begin / gm_load_views / gm_load_views_commit take
+# (Simulator.load_views). It does not depend on the layout: a cluster snapshot cuts into row shards'
+# snapshots (slice_rows with each shard's shard_layout()) and the shards' snapshots join back
+# (join_rows). A row shard knows its own nodes' flags only, so view_snapshot of a shard takes the
+# cluster's flags from the caller (`failed`), or leaves the other nodes' flags 0 for join_rows to fill.
+VIEW_KEYS = ("t", "n0", "views", "heartbeat", "failed", "targets", "counts")
+VIEW_NODE_KEYS = ("t", "n0", "heartbeat", "failed", "targets", "counts")  # view_save_dir's nodes.npz
+
+
+def _view_rows(v, chunk_rows):
+    return max(1, int(chunk_rows)) if chunk_rows is not None else max(1, (64 << 20) // (8 * v))
+
+
+def _check_view_snap(snap):
+    missing = [k for k in VIEW_KEYS if k not in snap]
+    if missing:
+        raise ValueError(f"not a view snapshot: keys {missing} missing")
+    views = snap["views"]
+    if views.ndim != 2 or views.dtype != np.uint64:
+        raise ValueError(f"views must be uint64 [nloc][V], not {views.dtype} {views.shape}")
+    nloc, n, n0 = views.shape[0], len(snap["failed"]), int(snap["n0"])
+    shapes = {"heartbeat": (nloc,), "counts": (nloc,), "targets": (nloc, 5)}
+    for k, want in shapes.items():
+        if tuple(np.shape(snap[k])) != want:
+            raise ValueError(f"{k} of shape {np.shape(snap[k])}, the views cover {nloc} nodes")
+    if n0 < 0 or n0 + nloc > n:
+        raise ValueError(f"nodes [{n0}, {n0 + nloc}) of a cluster of {n}")
+    return n0, nloc, n
+
+
+def _view_nodes(sim, failed=None):
+    n0, nloc = sim.shard_layout()
+    st = sim.read_nodes()
+    tg, cnt = sim.read_targets()
+    if failed is None:
+        failed = np.zeros(sim.n, dtype=np.int32)
+    else:
+        failed = np.array(failed, dtype=np.int32).reshape(sim.n)
+    failed[n0:n0 + nloc] = st[:, 2]
+    return {"t": int(sim.time), "n0": n0, "heartbeat": st[:, 3].copy(), "failed": failed, "targets": tg, "counts": cnt}
+
+
+def view_snapshot(sim, failed=None):
+    """The state of a PARTIAL context between two ticks (a row shard: its own nodes). failed: the crash
+    flags of the whole cluster for a row shard's snapshot (its own nodes' flags are read from it)."""
+    n0, nloc = sim.shard_layout()
+    return dict(_view_nodes(sim, failed), views=sim.read_views(n0, nloc))
+
+
+def view_restore(sim, snap, chunk_rows=None):
+    """Load a view snapshot into a PARTIAL context that owns exactly its nodes; tick snap["t"] runs next."""
+    n0, nloc, n = _check_view_snap(snap)
+    if (n0, nloc) != tuple(sim.shard_layout()) or n != sim.n:
+        raise ValueError(f"a snapshot of nodes [{n0}, {n0 + nloc}) of {n} for a context of "
+                         f"{tuple(sim.shard_layout())} of {sim.n}: cut it with slice_rows")
+    sim.load_views(snap["t"], snap["views"], snap["heartbeat"], snap["failed"], snap["targets"], snap["counts"],
+                   chunk_rows=chunk_rows)
+
+
+def slice_rows(snap, n0, nloc):
+    """A snapshot cut to the nodes [n0, n0 + nloc) (a row shard's shard_layout()); failed stays the cluster's."""
+    s0, sl, _ = _check_view_snap(snap)
+    if nloc <= 0 or n0 < s0 or n0 + nloc > s0 + sl:
+        raise ValueError(f"nodes [{n0}, {n0 + nloc}) of a snapshot of nodes [{s0}, {s0 + sl})")
+    a, b = n0 - s0, n0 - s0 + nloc
+    out = dict(snap)
+    out["n0"] = int(n0)
+    for k in ("views", "heartbeat", "targets", "counts"):
+        out[k] = np.ascontiguousarray(snap[k][a:b])
+    return out
+
+
+def join_rows(snaps):
+    """The row shards' snapshots (ascending, adjacent node ranges) as one snapshot. Each node's crash flag
+    is taken from the snapshot that covers it; nodes no snapshot covers keep the first one's flag."""
+    lay = [_check_view_snap(s) for s in snaps]
+    first = snaps[0]
+    for s, (n0, _, n), (p0, pl, _) in zip(snaps[1:], lay[1:], lay[:-1]):
+        if s["t"] != first["t"] or n != lay[0][2] or n0 != p0 + pl or s["views"].shape[1] != first["views"].shape[1]:
+            raise ValueError("the snapshots are not adjacent row ranges of one tick of one cluster")
+    out = dict(first)
+    for k in ("views", "heartbeat", "targets", "counts"):
+        out[k] = np.concatenate([s[k] for s in snaps])
+    failed = np.array(first["failed"], dtype=np.int32)
+    for s, (n0, nloc, _) in zip(snaps, lay):
+        failed[n0:n0 + nloc] = np.asarray(s["failed"])[n0:n0 + nloc]
+    out["failed"] = failed
+    return out
+
+
+def view_save_dir(sim, path, chunk_rows=None, failed=None):
+    """Stream the state of a PARTIAL context to the directory `path`: views.npy (uint64 [nloc][V], written
+    block by block through read_views, chunk_rows nodes at a time) and nodes.npz (the other keys)."""
+    os.makedirs(path, exist_ok=True)
+    n0, nloc = sim.shard_layout()
+    v = sim.cfg.view or 32
+    views = np.lib.format.open_memmap(os.path.join(path, "views.npy"), mode="w+", dtype=np.uint64, shape=(nloc, v))
+    m = min(nloc, _view_rows(v, chunk_rows))
+    for r0 in range(0, nloc, m):
+        k = min(m, nloc - r0)
+        views[r0:r0 + k] = sim.read_views(n0 + r0, k)
+    views.flush()
+    del views
+    nodes = _view_nodes(sim, failed)
+    with open(os.path.join(path, "nodes.npz"), "wb") as f:
+        np.savez(f, **{k: np.asarray(nodes[k], dtype=np.int32) for k in VIEW_NODE_KEYS})
+
+
+def view_load_dir(path):
+    """The snapshot view_save_dir wrote, views memory-mapped read-only (view_restore loads them block by block)."""
+    with np.load(os.path.join(path, "nodes.npz")) as z:
+        missing = [k for k in VIEW_NODE_KEYS if k not in z.files]
+        if missing:
+            raise ValueError(f"{path}: nodes.npz lacks {missing}")
+        snap = {k: z[k].copy() for k in VIEW_NODE_KEYS}
+    snap["t"], snap["n0"] = int(snap["t"]), int(snap["n0"])
+    snap["views"] = np.load(os.path.join(path, "views.npy"), mmap_mode="r")
+    _check_view_snap(snap)
+    return snap

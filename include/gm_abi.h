@@ -250,7 +250,10 @@ int gm_read_views(gm_ctx *ctx, int32_t r0, int32_t count, uint64_t *out);
 int gm_read_nodes(gm_ctx *ctx, int32_t *state4);
 /* SCALED: the gossip targets every node drew in the last tick (the gossipnodes of nodeLoopOps,
  * MP1Node.cpp:449-489, as node indices; [n][5], unused slots 0) and their counts [n] -- with the
- * tables and node state, the whole state between two ticks */
+ * tables and node state, the whole state between two ticks.
+ * PARTIAL: the same for this context's own nodes, [nloc][5] global node indices and counts [nloc]
+ * (a row shard reads its own nodes, as gm_read_views does). A crashed node reports the targets of its
+ * last tick until the next tick freezes it, count 0 from then on. */
 int gm_read_targets(gm_ctx *ctx, int32_t *targets, int32_t *counts);
 /* ---- SCALED: load a cluster state into a context, the inverse of gm_read_table / gm_read_nodes /
  * gm_read_targets (the oracle's oc_load_scaled, oracle/ref_cpu.c). The state between two ticks is
@@ -287,6 +290,50 @@ int gm_load_commit(gm_ctx *ctx, const int32_t *heartbeat, const int32_t *failed,
  * gm_set_timing is on (HIP events around each launch, one wait per block), the milliseconds spent in
  * the check kernel and in the encode kernel} */
 int gm_load_stats(gm_ctx *ctx, double stats[4]);
+
+/* ---- PARTIAL: load a view state into a context, the inverse of gm_read_views / gm_read_nodes /
+ * gm_read_targets. The state between two ticks -- every node's final view of tick t - 1, the heartbeat
+ * counters, the crash flags, the targets drawn in t - 1 -- does not depend on the layout: a state read
+ * from one context loads into G row shards (each its own nodes) and the other way round. FAITHFUL /
+ * SCALED contexts and contexts recording msgcount (their history for ticks < t would be missing)
+ * return GM_EUNSUPPORTED.
+ *
+ * gm_load_views_begin settles the run so far on both streams, discards undrained events, allocates one
+ * device staging buffer of at most 256 MiB (max(1, 256 MiB / 8V) views per block; GM_LOAD_STAGE_ROWS
+ * lowers that for tests; the commit frees it) and puts the context into the loading state: until
+ * gm_load_views_commit succeeds, gm_tick, gm_partial_loopback_tick and gm_set_failed return GM_ESTATE
+ * and the read-back functions are undefined. t is the next tick to run; it must be a tick a created
+ * context could be at (init_t0 + 1 for an init_t0 gm_create accepts: 6 <= t <= 16384), else GM_EINVAL.
+ * gm_load_views gives the views of nodes [r0, r0 + count), global indices inside this context's
+ * [n0, n0 + nloc): [count][V], exactly what gm_read_views(r0, count) returns. Blocks in any order,
+ * each node exactly once (a repeat, or a commit with nodes missing: GM_ESTATE).
+ * gm_load_views_commit gives the heartbeat counters [nloc], the crash flags of the WHOLE cluster [n]
+ * (every row shard the same array, as with gm_set_failed), the targets [nloc][5] and counts [nloc] of
+ * this context's nodes as gm_read_targets returns them, builds the inboxes of tick t and sets the time
+ * to t. The context is then as tick t - 1 would have left it: no pending events, the error flag clear,
+ * the exchange block capacities and the crash-set hash following the loaded flags. A row shard's
+ * received lists are not part of the state: its next tick first replays the exchange of tick t - 1
+ * (every member of the group -- all RCCL ranks, all G loopback contexts -- must have committed a load;
+ * a group where only some have latches GM_ESTATE on all of them).
+ *
+ * Everything is checked on the device before anything of the block or the commit is written.
+ * GM_EINVAL for a view: an id outside [1, n]; ids not strictly ascending; a non-empty slot after an
+ * empty one; an even heartbeat; a heartbeat above 2(t - 1) - 1; and, found at the commit, where the
+ * flags are known, an entry of a live node's view aged GM_VIEW_AGES or more (what gm_view_census would
+ * reject). GM_EINVAL at the commit: a node whose own entry is missing or not {heartbeat - 1}; a live
+ * node whose heartbeat is not 2(t - 1); a crashed node whose heartbeat is odd or above 2(t - 1);
+ * failed not 0 / 1; counts outside 0..5; a target outside [0, n), equal to the node itself, named
+ * twice, or not an entry of the node's own view; a crashed node with targets that did not run tick
+ * t - 1. GM_ERANGE: more lists for one receiver than its inbox holds (for lists sent by other row
+ * shards, and for a packed exchange block past its capacity, at the tick that replays the exchange).
+ * After a failed call the context stays in the loading state; gm_load_views_begin starts over. */
+int gm_load_views_begin(gm_ctx *ctx, int32_t t);
+int gm_load_views(gm_ctx *ctx, int32_t r0, int32_t count, const uint64_t *views);
+int gm_load_views_commit(gm_ctx *ctx, const int32_t *heartbeat, const int32_t *failed, const int32_t *targets,
+                         const int32_t *counts);
+/* stats = {views stored since the last gm_load_views_begin, bytes of its staging buffer, and, while
+ * gm_set_timing is on, the milliseconds spent in the check kernel and in the store kernel} */
+int gm_load_views_stats(gm_ctx *ctx, double stats[4]);
 
 /* ---- SCALED: the membership census, reduced on the device (the table is not copied to the host). */
 #define GM_CENSUS_LAGS 64
