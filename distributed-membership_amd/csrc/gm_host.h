@@ -8,7 +8,8 @@
 //   gm_host_partial.hip   PARTIAL: state, tick, the row shards' exchange
 //   gm_host_events.hip    event drains, detection recorder, msgcount
 //   gm_host_read.hip      read-backs: rows, tables, views, nodes, targets, the censuses
-//   gm_host_load.hip      gm_load_*, gm_load_views_*
+//   gm_host_stage.hip     the staged block of gm_read_rows and the loads: size, timing, stats
+//   gm_host_load.hip      gm_load_*, gm_load_views_*: one block loop, one commit tail
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -60,52 +61,30 @@ struct gm_view_census_scratch {
   int64_t nfailed = -1;              // gm_ctx.nfailed when the bitmap was last built (-1: never)
 };
 
-// SCALED state loading (gm_load_begin .. gm_load_commit). One device block (blob, freed by the
-// commit): the staged (hb, ts) of up to cap rows, their base ticks, every row's own entry
-// as staged, the node arrays of the commit, the status word of a call's checks.
-struct gm_load_stage {
-  bool loading = false;              // between gm_load_begin and a successful gm_load_commit
-  bool voided = false;               // a load call failed: only gm_load_begin starts over
-  int t = 0;                         // gm_load_begin's t
-  int cap = 0;                       // staged rows per encode launch
-  void *blob = nullptr;
-  size_t bytes = 0;
-  int32_t *hb = nullptr, *ts = nullptr, *base = nullptr, *own = nullptr, *nodes = nullptr;
-  uint32_t *status = nullptr;
-  std::vector<uint8_t> seen;         // rows given so far
-  int64_t rows = 0;
-  double ms[2] = {0, 0};             // gm_set_timing on: ms in gm_l_check / gm_l_encode since gm_load_begin
+#define GM_STAGE_BYTES (256ull << 20)  // what a staged call's rows of one launch may take on the device
+
+// What every staged call keeps (gm_read_rows, gm_load_*, gm_load_views_*): rows cross between the host
+// and the state through one device block, cap rows per launch, each launch checked by the call's kernels
+// through the status word at the block's end. The planes in front of it are the call's own, carved out
+// where they are used (gm_host_load.hip, gm_host_read.hip). gm_host_stage.hip has the helpers.
+struct gm_stage {
+  void *blob = nullptr;              // the device block
+  size_t bytes = 0;                  // its size as the stats report it (gm_read_rows: of the planes alone)
+  int cap = 0;                       // rows per launch
+  uint32_t *status = nullptr;        // the status word of the call's kernels (in the block)
+  int64_t rows = 0;                  // rows done: since the begin (loads), since gm_create (gm_read_rows)
+  double ms[2] = {0, 0};             // gm_set_timing on: ms in the call's two timed spans (stage_span)
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
 };
 
-// PARTIAL view loading (gm_load_views_begin .. gm_load_views_commit). One device block (blob, at most
-// 256 MiB, freed by the commit): the staged views of up to cap nodes -- the commit stages the node
-// arrays through the same rows, ncap nodes at a time --, the "given" bitmap of this context's nodes,
-// the status word of a call's checks.
-struct gm_view_load_stage {
-  bool loading = false;              // between gm_load_views_begin and a successful gm_load_views_commit
-  bool voided = false;               // a load call failed: only gm_load_views_begin starts over
-  bool xpending = false;             // row shards: committed, the exchange of tick t - 1 is replayed by the next tick
-  int t = 0;                         // gm_load_views_begin's t
-  int cap = 0, ncap = 0;             // staged views per launch; staged nodes per launch of the commit
-  void *blob = nullptr;
-  size_t bytes = 0;
-  uint64_t *rows = nullptr;          // [cap][V]
-  uint32_t *given = nullptr, *status = nullptr;
-  std::vector<uint8_t> seen;         // this context's nodes given so far
-  int64_t nrows = 0;
-  double ms[2] = {0, 0};             // gm_set_timing on: ms in gm_pl_check / gm_pl_store since the begin
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-};
-
-// SCALED rows decoded on the device (gm_read_rows): one device block, allocated by the first call and
-// reused -- the staging planes hb, ts [cap][w] of one decode launch, then the kernel's status word
-struct gm_read_stage {
-  uint8_t *blob = nullptr;
-  int cap = 0;                       // rows per decode launch
-  int64_t rows = 0;                  // rows decoded since gm_create
-  double ms[2] = {0, 0};             // gm_set_timing on: ms in gm_r_decode / in the device-to-host copies
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+// A state load, begin .. rows .. commit: c->ld (SCALED, gm_load_*), c->vl (PARTIAL, gm_load_views_*).
+// The block is allocated by the begin and freed by the commit.
+struct gm_load_stage : gm_stage {
+  bool loading = false;              // between the begin and a successful commit
+  bool voided = false;               // a load call failed: only the begin starts over
+  bool xpending = false;             // PARTIAL row shards: committed, the exchange of tick t - 1 is replayed by the next tick
+  int t = 0;                         // the begin's t
+  std::vector<uint8_t> seen;         // this context's rows given so far
 };
 
 // FAITHFUL, host side of FState
@@ -182,11 +161,11 @@ struct gm_ctx {
   SState s{};  // SCALED
   gm_census_scratch cen;
   gm_load_stage ld;
-  gm_read_stage rd;
+  gm_stage rd;
   PState p{};  // PARTIAL
   gm_partial_host ph;
   gm_view_census_scratch vc;
-  gm_view_load_stage vl;
+  gm_load_stage vl;
   gm_shard_exchange xch;  // SCALED column shards, PARTIAL row shards
 };
 
@@ -305,9 +284,13 @@ int partial_caps(gm_ctx *c);
 // gm_host_events.hip
 int before_tick_events(gm_ctx *c);
 
-// gm_host_load.hip, gm_host_read.hip
-void load_destroy(gm_ctx *c);
-void vload_destroy(gm_ctx *c);
-void read_destroy(gm_ctx *c);
+// gm_host_stage.hip
+int stage_cap(size_t budget, size_t row_bytes, size_t rows, const char *env);
+int stage_alloc(gm_stage &st, int cap, size_t bytes, size_t status_off, const char *what);
+void stage_free(gm_stage &st);
+void stage_destroy(gm_stage &st, bool owned);
+int stage_mark(gm_ctx *c, gm_stage &st, int k);
+int stage_span(gm_ctx *c, gm_stage &st, int slot, int from, int to);
+int stage_stats(const gm_ctx *c, int mode, const gm_stage *st, double stats[4]);
 
 }  // namespace gmh

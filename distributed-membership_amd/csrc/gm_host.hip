@@ -117,9 +117,9 @@ extern "C" int gm_destroy(gm_ctx *c) {
   if (c->xch.stream) (void)hipStreamSynchronize(c->xch.stream);
   if (c->comm) (void)ncclCommDestroy(c->comm);
   for (void *p : c->allocs) (void)hipFree(p);
-  load_destroy(c);
-  vload_destroy(c);
-  read_destroy(c);
+  stage_destroy(c->ld, true);
+  stage_destroy(c->vl, true);
+  stage_destroy(c->rd, false);  // its block was in `allocs`
   destroy_scaled(c);
   destroy_faithful(c);
   for (hipEvent_t e : {c->e0, c->e1, c->k0, c->k1})

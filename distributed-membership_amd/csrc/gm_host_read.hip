@@ -207,8 +207,6 @@ extern "C" int gm_read_table(gm_ctx *c, int32_t r0, int32_t count, int32_t *hb, 
 // gm_read_rows (gm_read.hip has the kernel and what it checks): what gm_read_table returns, at a cost
 // that follows count, not n. A read-back: it settles the enqueued ticks, reports their device error,
 // and writes nothing but its own staging block.
-#define GM_READ_STAGE_BYTES (256ull << 20)  // the (hb, ts) planes of one decode launch
-
 extern "C" int gm_read_rows(gm_ctx *c, int32_t r0, int32_t count, int32_t *hb, int32_t *ts) {
   if (!c) return GM_EINVAL;
   if (c->cfg.mode != GM_MODE_SCALED) return GM_EUNSUPPORTED;
@@ -217,56 +215,38 @@ extern "C" int gm_read_rows(gm_ctx *c, int32_t r0, int32_t count, int32_t *hb, i
   if (count == 0) return GM_OK;
   const SState &s = c->s;
   const size_t w = (size_t)s.w, row_bytes = 2 * sizeof(int32_t) * w;
-  if (!c->rd.blob) {
-    size_t cap = std::min<size_t>((size_t)c->n, std::max<size_t>(1, GM_READ_STAGE_BYTES / row_bytes));
-    if (getenv("GM_READ_STAGE_ROWS"))  // diagnostics (tests): smaller decode launches
-      cap = std::max<size_t>(1, std::min<size_t>(cap, (size_t)atol(getenv("GM_READ_STAGE_ROWS"))));
-    TRY(dalloc(c, &c->rd.blob, cap * row_bytes + 16));
-    c->rd.cap = (int)cap;
+  gm_stage &rd = c->rd;  // allocated by the first call and reused, in `allocs`: the planes hb, ts [cap][w]
+  if (!rd.blob) {        // of one decode launch (bytes: theirs), then the status word
+    uint8_t *blob = nullptr;
+    const int cap = stage_cap(GM_STAGE_BYTES, row_bytes, (size_t)c->n, "GM_READ_STAGE_ROWS");
+    TRY(dalloc(c, &blob, cap * row_bytes + 16));
+    rd.blob = blob;
+    rd.cap = cap;
+    rd.bytes = cap * row_bytes;
+    rd.status = (uint32_t *)(blob + rd.bytes);
   }
-  int32_t *stage = (int32_t *)c->rd.blob;
-  uint32_t *d_status = (uint32_t *)(c->rd.blob + (size_t)c->rd.cap * row_bytes);
-  if (c->timing)
-    for (hipEvent_t &e : c->rd.ev)
-      if (!e) HIPCHECK(hipEventCreate(&e));
-  HIPCHECK(ctx_memset(c, d_status, 0, sizeof(uint32_t)));
+  int32_t *stage = (int32_t *)rd.blob;
+  HIPCHECK(ctx_memset(c, rd.status, 0, sizeof(uint32_t)));
   const int par = (c->t - 1) & 1;
-  for (int off = 0; off < count; off += c->rd.cap) {
-    const int m = std::min(c->rd.cap, count - off);
-    if (c->timing) HIPCHECK(hipEventRecord(c->rd.ev[0], c->stream));
-    HIPCHECK(gm_launch_read_decode(s, par, r0 + off, m, stage, d_status, c->stream));
-    if (c->timing) HIPCHECK(hipEventRecord(c->rd.ev[1], c->stream));
+  for (int off = 0; off < count; off += rd.cap) {  // gm_set_timing on: ms[0] the decode kernel, ms[1] the copies
+    const int m = std::min(rd.cap, count - off);
+    TRY(stage_mark(c, rd, 0));
+    HIPCHECK(gm_launch_read_decode(s, par, r0 + off, m, stage, rd.status, c->stream));
+    TRY(stage_mark(c, rd, 1));
     // nothing of the block is handed out before its checks pass
-    TRY(kernel_status(c, d_status, GM_ESTATE, "gm_read_rows: the stored state is inconsistent (flags 0x%x)"));
+    TRY(kernel_status(c, rd.status, GM_ESTATE, "gm_read_rows: the stored state is inconsistent (flags 0x%x)"));
     HIPCHECK(ctx_memcpy(c, hb + (size_t)off * w, stage, sizeof(int32_t) * m * w, hipMemcpyDeviceToHost));
     HIPCHECK(ctx_memcpy(c, ts + (size_t)off * w, stage + (size_t)m * w, sizeof(int32_t) * m * w, hipMemcpyDeviceToHost));
-    if (c->timing) {
-      float a = 0, b = 0;
-      HIPCHECK(hipEventRecord(c->rd.ev[2], c->stream));
-      HIPCHECK(hipEventSynchronize(c->rd.ev[2]));
-      HIPCHECK(hipEventElapsedTime(&a, c->rd.ev[0], c->rd.ev[1]));
-      HIPCHECK(hipEventElapsedTime(&b, c->rd.ev[1], c->rd.ev[2]));
-      c->rd.ms[0] += a;
-      c->rd.ms[1] += b;
-    }
-    c->rd.rows += m;
+    TRY(stage_mark(c, rd, 2));
+    TRY(stage_span(c, rd, 0, 0, 1));
+    TRY(stage_span(c, rd, 1, 1, 2));
+    rd.rows += m;
   }
   return GM_OK;
-}
-
-void gmh::read_destroy(gm_ctx *c) {  // the staging block is in `allocs`
-  for (hipEvent_t e : c->rd.ev)
-    if (e) (void)hipEventDestroy(e);
 }
 
 extern "C" int gm_read_rows_stats(gm_ctx *c, double stats[4]) {
-  if (!c || !stats) return GM_EINVAL;
-  if (c->cfg.mode != GM_MODE_SCALED) return GM_EUNSUPPORTED;
-  stats[0] = (double)c->rd.rows;
-  stats[1] = (double)c->rd.cap * 2 * sizeof(int32_t) * (double)c->s.w;
-  stats[2] = c->rd.ms[0];
-  stats[3] = c->rd.ms[1];
-  return GM_OK;
+  return stage_stats(c, GM_MODE_SCALED, c ? &c->rd : nullptr, stats);
 }
 
 extern "C" int gm_read_views(gm_ctx *c, int32_t r0, int32_t count, uint64_t *out) {
@@ -316,12 +296,28 @@ extern "C" int gm_read_nodes(gm_ctx *c, int32_t *st4) {
   return GM_OK;
 }
 
+// One line of the dump: "t node inited ingroup failed heartbeat count", then the count entries " id:hb:ts"
+struct DumpEntry {
+  int id, hb, ts;
+};
+
+static void dump_line(std::string &out, int t, int node, const int32_t *st4, const std::vector<DumpEntry> &ent) {
+  char tmp[96];
+  snprintf(tmp, sizeof tmp, "%d %d %d %d %d %d %d", t, node, st4[0], st4[1], st4[2], st4[3], (int)ent.size());
+  out += tmp;
+  for (const DumpEntry &e : ent) {
+    snprintf(tmp, sizeof tmp, " %d:%d:%d", e.id, e.hb, e.ts);
+    out += tmp;
+  }
+  out += "\n";
+}
+
 extern "C" int gm_dump_tables(gm_ctx *c, char *buf, size_t cap, size_t *len) {
   if (!c || !len) return GM_EINVAL;
   std::vector<int32_t> st(4 * (size_t)c->n);
   TRY(gm_read_nodes(c, st.data()));
   std::string out;
-  char tmp[96];
+  std::vector<DumpEntry> ent;
   const int t = c->t - 1;
   if (c->cfg.mode == GM_MODE_PARTIAL) {  // the V-entry lists (id order) of the last tick, one copy
     const PState &p = c->p;          // a row shard renders its own nodes (global indices)
@@ -329,47 +325,29 @@ extern "C" int gm_dump_tables(gm_ctx *c, char *buf, size_t cap, size_t *len) {
     HIPCHECK(ctx_memcpy(c, all.data(), p.lists + (size_t)(t & 1) * p.rows * p.V, sizeof(uint64_t) * all.size(),
                        hipMemcpyDeviceToHost));
     for (int i = 0; i < p.nloc; i++) {
-      const uint64_t *row = all.data() + (size_t)i * p.V;
-      int cnt = 0;
-      for (int j = 0; j < p.V; j++) cnt += row[j] != 0;
-      snprintf(tmp, sizeof tmp, "%d %d %d %d %d %d %d", t, p.n0 + i, st[4 * i], st[4 * i + 1], st[4 * i + 2],
-               st[4 * i + 3], cnt);
-      out += tmp;
+      ent.clear();
       for (int j = 0; j < p.V; j++) {
-        if (!row[j]) continue;
-        const int h = (int)(uint32_t)row[j];
-        snprintf(tmp, sizeof tmp, " %d:%d:%d", (int)(row[j] >> 32), h, (h + 1) / 2);
-        out += tmp;
+        const uint64_t e = all[(size_t)i * p.V + j];
+        const int h = (int)(uint32_t)e;
+        if (e) ent.push_back({(int)(e >> 32), h, (h + 1) / 2});
       }
-      out += "\n";
+      dump_line(out, t, p.n0 + i, &st[4 * (size_t)i], ent);
     }
-    *len = out.size();
-    if (!buf || cap < out.size()) return GM_ERANGE;
-    memcpy(buf, out.data(), out.size());
-    return GM_OK;
-  }
-  std::vector<int32_t> rh, rt;
-  ScaledSnapshot snap;
-  if (c->cfg.mode == GM_MODE_SCALED) TRY(snap.load(c));
-  for (int i = 0; i < c->n; i++) {
-    int w;
-    if (c->cfg.mode == GM_MODE_SCALED) {
-      TRY(snap.decode(c, i, rh, rt));
-      w = c->s.w;
-    } else {
-      TRY(read_table_row(c, i, rh, rt, w));
+  } else {
+    const bool scaled = c->cfg.mode == GM_MODE_SCALED;
+    const int c0 = scaled ? c->s.c0 : 0;
+    std::vector<int32_t> rh, rt;
+    ScaledSnapshot snap;
+    if (scaled) TRY(snap.load(c));
+    for (int i = 0; i < c->n; i++) {
+      int w = c->s.w;
+      if (scaled) TRY(snap.decode(c, i, rh, rt));
+      else TRY(read_table_row(c, i, rh, rt, w));
+      ent.clear();
+      for (int j = 0; j < w; j++)
+        if (rh[j] >= 0) ent.push_back({c0 + j + 1, rh[j], rt[j]});
+      dump_line(out, t, i, &st[4 * (size_t)i], ent);
     }
-    int cnt = 0;
-    const int c0 = c->cfg.mode == GM_MODE_SCALED ? c->s.c0 : 0;
-    for (int j = 0; j < w; j++) cnt += rh[j] >= 0;
-    snprintf(tmp, sizeof tmp, "%d %d %d %d %d %d %d", t, i, st[4 * i], st[4 * i + 1], st[4 * i + 2], st[4 * i + 3], cnt);
-    out += tmp;
-    for (int j = 0; j < w; j++) {
-      if (rh[j] < 0) continue;
-      snprintf(tmp, sizeof tmp, " %d:%d:%d", c0 + j + 1, rh[j], rt[j]);
-      out += tmp;
-    }
-    out += "\n";
   }
   *len = out.size();
   if (!buf || cap < out.size()) return GM_ERANGE;
@@ -379,26 +357,20 @@ extern "C" int gm_dump_tables(gm_ctx *c, char *buf, size_t cap, size_t *len) {
 
 extern "C" int gm_read_targets(gm_ctx *c, int32_t *targets, int32_t *counts) {
   if (!c || !targets || !counts) return GM_EINVAL;
-  if (c->cfg.mode == GM_MODE_PARTIAL) {  // this context's own nodes: [nloc][5] global indices, counts [nloc]
-    const size_t nl = (size_t)c->p.nloc;
-    std::vector<int32_t> st(nl * 4);
+  const bool part = c->cfg.mode == GM_MODE_PARTIAL;
+  if (part) {  // this context's own nodes: [nloc][5] global indices, counts [nloc]
     if (c->xch.stream) HIPCHECK(hipStreamSynchronize(c->xch.stream));
     HIPCHECK(hipStreamSynchronize(c->stream));
-    HIPCHECK(ctx_memcpy(c, targets, c->p.targets, sizeof(int32_t) * nl * GM_FANOUT, hipMemcpyDeviceToHost));
-    HIPCHECK(ctx_memcpy(c, st.data(), c->p.rowstat, sizeof(int32_t) * nl * 4, hipMemcpyDeviceToHost));
-    for (size_t r = 0; r < nl; r++) {
-      counts[r] = st[r * 4 + 3];
-      for (int q = counts[r]; q < GM_FANOUT; q++) targets[r * GM_FANOUT + q] = 0;
-    }
-    return check_err(c);
+  } else if (c->cfg.mode == GM_MODE_SCALED) {
+    TRY(draw_settle(&c, 1));
+  } else {
+    return GM_EUNSUPPORTED;
   }
-  if (c->cfg.mode != GM_MODE_SCALED) return GM_EUNSUPPORTED;
-  TRY(draw_settle(&c, 1));
-  const size_t n = (size_t)c->n;
-  std::vector<int32_t> st(n * 4);
-  HIPCHECK(ctx_memcpy(c, targets, c->s.targets, sizeof(int32_t) * n * GM_FANOUT, hipMemcpyDeviceToHost));
-  HIPCHECK(ctx_memcpy(c, st.data(), c->s.rowstat, sizeof(int32_t) * n * 4, hipMemcpyDeviceToHost));
-  for (size_t r = 0; r < n; r++) {
+  const size_t rows = part ? (size_t)c->p.nloc : (size_t)c->n;
+  std::vector<int32_t> st(rows * 4);
+  HIPCHECK(ctx_memcpy(c, targets, part ? c->p.targets : c->s.targets, sizeof(int32_t) * rows * GM_FANOUT, hipMemcpyDeviceToHost));
+  HIPCHECK(ctx_memcpy(c, st.data(), part ? c->p.rowstat : c->s.rowstat, sizeof(int32_t) * rows * 4, hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < rows; r++) {
     counts[r] = st[r * 4 + 3];
     for (int q = counts[r]; q < GM_FANOUT; q++) targets[r * GM_FANOUT + q] = 0;
   }

@@ -67,16 +67,53 @@ GM_VIEW_AGES, GM_VIEW_SIZES = 32, 33
 VIEW_DTYPE = np.dtype([("hb_min", "<i4"), ("hb_max", "<i4"), ("holders", "<u4"), ("stale", "<u4"), ("hb_sum", "<u8")])
 assert VIEW_DTYPE.itemsize == ctypes.sizeof(GmViewRec) == 24
 
-EXPORTS = ["gm_detect_record", "gm_detect", "gm_detect_timeline", "gm_parse_conf", "gm_create", "gm_destroy", "gm_tick", "gm_sync", "gm_time", "gm_rand", "gm_set_failed",
-           "gm_set_dropmsg", "gm_drain_events", "gm_event_counts", "gm_msgcount", "gm_read_row", "gm_read_table", "gm_read_nodes",
-           "gm_dump_tables", "gm_tick_stats", "gm_set_timing", "gm_last_kernel_ms", "gm_crash_set", "gm_strerror",
-           "gm_comm_unique_id", "gm_comm_init", "gm_shard_layout", "gm_shard_merge", "gm_shard_draw",
-           "gm_shard_accept", "gm_shard_end_tick", "gm_shard_loopback", "gm_partial_loopback_tick",
-           "gm_shard_exchange_bytes", "gm_keep_events", "gm_event_totals", "gm_read_views", "gm_shard_stub",
-           "gm_msgcount_record", "gm_comm_info", "gm_shard_export", "gm_shard_import", "gm_pool_info", "gm_shard_loopback_tick", "gm_read_targets",
-           "gm_load_begin", "gm_load_rows", "gm_load_commit", "gm_load_stats", "gm_census", "gm_view_census",
-           "gm_read_rows", "gm_read_rows_stats",
-           "gm_load_views_begin", "gm_load_views", "gm_load_views_commit", "gm_load_views_stats"]
+_P = ctypes.POINTER
+_ctx, _i32, _i64, _u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
+_f64, _sz = ctypes.c_double, ctypes.c_size_t
+_load4 = [_ctx, _P(_i32), _P(_i32), _P(_i32), _P(_i32)]  # a load's commit: heartbeat, failed, targets, counts
+
+# Every entry point of include/gm_abi.h that returns a status: its argument types. A new entry point
+# is declared in the header and listed here (tests/test_abi.py compares the two).
+SIGNATURES = {
+    "gm_parse_conf": [ctypes.c_char_p, _P(GmConfig)],
+    "gm_create": [_P(GmConfig), _P(_ctx)],
+    "gm_destroy": [_ctx], "gm_tick": [_ctx], "gm_sync": [_ctx],
+    "gm_time": [_ctx, _P(_i32)], "gm_rand": [_ctx, _P(_i32)],
+    "gm_set_failed": [_ctx, _P(_i32), _i32], "gm_set_dropmsg": [_ctx, _i32],
+    "gm_drain_events": [_ctx, _P(GmEvent), _sz, _P(_sz)],
+    "gm_event_counts": [_ctx, _P(_u64)], "gm_event_totals": [_ctx, _P(_u64)],
+    "gm_keep_events": [_ctx, _i32], "gm_shard_stub": [_ctx, _i32], "gm_read_views": [_ctx, _i32, _i32, _P(_u64)],
+    "gm_msgcount": [_ctx, _i32, _P(_i32), _P(_i32)],
+    "gm_msgcount_record": [_ctx, _i32],
+    "gm_detect_record": [_ctx, _i32], "gm_detect": [_ctx, _P(GmDetectRec)],
+    "gm_detect_timeline": [_ctx, _i32, _P(_u64)],
+    "gm_read_row": [_ctx, _i32, _i32, _i32, _P(_i32), _P(_i32)],
+    "gm_read_table": [_ctx, _i32, _i32, _P(_i32), _P(_i32)],
+    "gm_read_nodes": [_ctx, _P(_i32)], "gm_read_targets": [_ctx, _P(_i32), _P(_i32)],
+    "gm_dump_tables": [_ctx, ctypes.c_char_p, _sz, _P(_sz)],
+    "gm_tick_stats": [_ctx, _P(_i64)], "gm_pool_info": [_ctx, _P(_i64)],
+    "gm_set_timing": [_ctx, _i32], "gm_last_kernel_ms": [_ctx, _P(ctypes.c_float)],
+    "gm_crash_set": [_i32, _i32, _u64, _P(_i32)],
+    "gm_comm_unique_id": [ctypes.c_char_p],
+    "gm_comm_init": [_ctx, ctypes.c_char_p, _i32, _i32],
+    "gm_comm_info": [_ctx, _P(_i32)],
+    "gm_shard_export": [_ctx, _i32, _i32, ctypes.c_void_p, _sz, _P(_sz)],
+    "gm_shard_import": [_ctx, _i32, _i32, ctypes.c_void_p, _sz],
+    "gm_shard_layout": [_ctx, _P(_i32), _P(_i32)],
+    "gm_shard_loopback": [_P(_ctx), _i32, _i32, _i32],
+    "gm_partial_loopback_tick": [_P(_ctx), _i32], "gm_shard_loopback_tick": [_P(_ctx), _i32],
+    "gm_shard_exchange_bytes": [_ctx, _P(_i64)],
+    "gm_shard_merge": [_ctx], "gm_shard_draw": [_ctx, _i32, _i32],
+    "gm_shard_accept": [_ctx, _i32, _P(_i32)], "gm_shard_end_tick": [_ctx],
+    "gm_load_begin": [_ctx, _i32], "gm_load_rows": [_ctx, _i32, _i32, _P(_i32), _P(_i32)],
+    "gm_load_commit": _load4, "gm_load_stats": [_ctx, _P(_f64)],
+    "gm_census": [_ctx, _P(GmCensusRec), _P(_u64)],
+    "gm_view_census": [_ctx, _P(GmViewRec), _P(_u64), _P(_u64)],
+    "gm_read_rows": [_ctx, _i32, _i32, _P(_i32), _P(_i32)], "gm_read_rows_stats": [_ctx, _P(_f64)],
+    "gm_load_views_begin": [_ctx, _i32], "gm_load_views": [_ctx, _i32, _i32, _P(_u64)],
+    "gm_load_views_commit": _load4, "gm_load_views_stats": [_ctx, _P(_f64)],
+}
+EXPORTS = list(SIGNATURES) + ["gm_strerror"]  # the one entry point that returns no status
 
 _lib = None
 
@@ -96,55 +133,11 @@ def load_library():
     if not os.path.exists(path):
         raise FileNotFoundError(f"libgm.so not built: {path} (run `make` at the repo root)")
     lib = ctypes.CDLL(path)
-    P = ctypes.POINTER
-    i32, u64, sz = ctypes.c_int32, ctypes.c_uint64, ctypes.c_size_t
-    sig = {
-        "gm_parse_conf": [ctypes.c_char_p, P(GmConfig)],
-        "gm_create": [P(GmConfig), P(ctypes.c_void_p)],
-        "gm_destroy": [ctypes.c_void_p], "gm_tick": [ctypes.c_void_p], "gm_sync": [ctypes.c_void_p],
-        "gm_time": [ctypes.c_void_p, P(i32)], "gm_rand": [ctypes.c_void_p, P(i32)],
-        "gm_set_failed": [ctypes.c_void_p, P(i32), i32], "gm_set_dropmsg": [ctypes.c_void_p, i32],
-        "gm_drain_events": [ctypes.c_void_p, P(GmEvent), sz, P(sz)],
-        "gm_event_counts": [ctypes.c_void_p, P(u64)], "gm_event_totals": [ctypes.c_void_p, P(u64)],
-        "gm_keep_events": [ctypes.c_void_p, i32], "gm_shard_stub": [ctypes.c_void_p, i32], "gm_read_views": [ctypes.c_void_p, i32, i32, P(u64)],
-        "gm_msgcount": [ctypes.c_void_p, i32, P(i32), P(i32)],
-        "gm_msgcount_record": [ctypes.c_void_p, i32],
-        "gm_detect_record": [ctypes.c_void_p, i32], "gm_detect": [ctypes.c_void_p, P(GmDetectRec)],
-        "gm_detect_timeline": [ctypes.c_void_p, i32, P(u64)],
-        "gm_read_row": [ctypes.c_void_p, i32, i32, i32, P(i32), P(i32)],
-        "gm_read_table": [ctypes.c_void_p, i32, i32, P(i32), P(i32)],
-        "gm_read_nodes": [ctypes.c_void_p, P(i32)], "gm_read_targets": [ctypes.c_void_p, P(i32), P(i32)],
-        "gm_dump_tables": [ctypes.c_void_p, ctypes.c_char_p, sz, P(sz)],
-        "gm_tick_stats": [ctypes.c_void_p, P(ctypes.c_int64)], "gm_pool_info": [ctypes.c_void_p, P(ctypes.c_int64)],
-        "gm_set_timing": [ctypes.c_void_p, i32], "gm_last_kernel_ms": [ctypes.c_void_p, P(ctypes.c_float)],
-        "gm_crash_set": [i32, i32, u64, P(i32)],
-        "gm_comm_unique_id": [ctypes.c_char_p],
-        "gm_comm_init": [ctypes.c_void_p, ctypes.c_char_p, i32, i32],
-        "gm_comm_info": [ctypes.c_void_p, P(i32)],
-        "gm_shard_export": [ctypes.c_void_p, i32, i32, ctypes.c_void_p, sz, P(sz)],
-        "gm_shard_import": [ctypes.c_void_p, i32, i32, ctypes.c_void_p, sz],
-        "gm_shard_layout": [ctypes.c_void_p, P(i32), P(i32)],
-        "gm_shard_loopback": [P(ctypes.c_void_p), i32, i32, i32],
-        "gm_partial_loopback_tick": [P(ctypes.c_void_p), i32], "gm_shard_loopback_tick": [P(ctypes.c_void_p), i32],
-        "gm_shard_exchange_bytes": [ctypes.c_void_p, P(ctypes.c_int64)],
-        "gm_shard_merge": [ctypes.c_void_p], "gm_shard_draw": [ctypes.c_void_p, i32, i32],
-        "gm_shard_accept": [ctypes.c_void_p, i32, P(i32)], "gm_shard_end_tick": [ctypes.c_void_p],
-        "gm_load_begin": [ctypes.c_void_p, i32], "gm_load_rows": [ctypes.c_void_p, i32, i32, P(i32), P(i32)],
-        "gm_load_commit": [ctypes.c_void_p, P(i32), P(i32), P(i32), P(i32)],
-        "gm_load_stats": [ctypes.c_void_p, P(ctypes.c_double)],
-        "gm_census": [ctypes.c_void_p, P(GmCensusRec), P(u64)],
-        "gm_view_census": [ctypes.c_void_p, P(GmViewRec), P(u64), P(u64)],
-        "gm_read_rows": [ctypes.c_void_p, i32, i32, P(i32), P(i32)],
-        "gm_read_rows_stats": [ctypes.c_void_p, P(ctypes.c_double)],
-        "gm_load_views_begin": [ctypes.c_void_p, i32], "gm_load_views": [ctypes.c_void_p, i32, i32, P(u64)],
-        "gm_load_views_commit": [ctypes.c_void_p, P(i32), P(i32), P(i32), P(i32)],
-        "gm_load_views_stats": [ctypes.c_void_p, P(ctypes.c_double)],
-    }
     # GM_AB_BUILD=1 (A/B scripts only): an older measurement build may lack newer entry points, which
     # are then left unbound. Otherwise every entry point must be present, whatever library GM_LIBRARY
     # names, so a stale libgm fails here and not at its first call of a missing symbol
     ab_build = os.environ.get("GM_AB_BUILD") == "1"
-    for name, args in sig.items():
+    for name, args in SIGNATURES.items():
         if ab_build and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
@@ -158,6 +151,11 @@ def load_library():
 
 def _ptr(a, ct=ctypes.c_int32):
     return a.ctypes.data_as(ctypes.POINTER(ct))
+
+
+def default_chunk_rows(width):
+    """rows per block of a state load or save when none is given: about 64 MiB at 8 * width bytes per row"""
+    return max(1, (64 << 20) // (8 * width))
 
 
 def crash_set(n, count, seed):
@@ -383,14 +381,18 @@ class Simulator:
             hb, ts = (a.reshape(-1)[:count * w].reshape(count, w) for a in (hb, ts))
         return hb, ts
 
+    def _stage_stats(self, name, spans):
+        """a staged call's stats (gm_*_stats): rows, the staging block's bytes and the ms in its two timed
+        spans, named by `spans` (the times only while set_timing is on)"""
+        v = (ctypes.c_double * 4)()
+        self._call(name, self.h, v)
+        return {"rows": int(v[0]), "staging_bytes": int(v[1]), spans[0]: float(v[2]), spans[1]: float(v[3])}
+
     def read_rows_stats(self):
         """{"rows", "staging_bytes", "stage_rows", "decode_ms", "copy_ms"} of read_rows since the context
         was created (the times only while set_timing is on); stage_rows: rows per decode launch"""
-        v = (ctypes.c_double * 4)()
-        self._call("gm_read_rows_stats", self.h, v)
-        w = self.shard_layout()[1]
-        return {"rows": int(v[0]), "staging_bytes": int(v[1]), "stage_rows": int(v[1]) // (8 * w),
-                "decode_ms": float(v[2]), "copy_ms": float(v[3])}
+        st = self._stage_stats("gm_read_rows_stats", ("decode_ms", "copy_ms"))
+        return dict(st, stage_rows=st["staging_bytes"] // (8 * self.shard_layout()[1]))
 
     def read_nodes(self):
         rows = self.shard_layout()[1] if self.mode == GM_MODE_PARTIAL else self.n  # a row shard: its own nodes
@@ -407,34 +409,39 @@ class Simulator:
         self._call("gm_read_targets", self.h, _ptr(tg), _ptr(cnt))
         return tg, cnt
 
+    def _load(self, calls, t, row0, tables, chunk_rows, heartbeat, failed, targets, counts):
+        """One state load: calls = the begin / rows / commit entry points; tables = the [rows][width]
+        arrays of the rows call, this context's rows from the cluster's row0 on, given chunk_rows at a
+        time (default: about 64 MiB); the node arrays cover the same rows, failed the whole cluster."""
+        rows, width = tables[0].shape
+        nodes = [np.ascontiguousarray(a, dtype=np.int32).reshape(shape) for a, shape in
+                 ((heartbeat, rows), (failed, self.n), (targets, (rows, 5)), (counts, rows))]
+        if chunk_rows is None:
+            chunk_rows = default_chunk_rows(width)
+        begin, give, commit = calls
+        self._call(begin, self.h, int(t))
+        for r0 in range(0, rows, chunk_rows):
+            m = min(chunk_rows, rows - r0)
+            block = [np.ascontiguousarray(a[r0:r0 + m]) for a in tables]  # of a memory-mapped table: read here
+            self._call(give, self.h, row0 + r0, m, *[_ptr(a, np.ctypeslib.as_ctypes_type(a.dtype)) for a in block])
+        self._call(commit, self.h, *[_ptr(a) for a in nodes])
+
     def load_state(self, t, hb, ts, heartbeat, failed, targets, counts, chunk_rows=None):
         """SCALED: replace the whole state between two ticks (gm_load_begin / gm_load_rows /
         gm_load_commit; the argument order of the oracle's load_state). hb / ts are int32 [n][w]
         over this context's columns (a shard: its own), -1 = absent, as read_table returns them;
         heartbeat / failed [n]; targets [n][5] and counts [n] as read_targets returns them; t is the
         next tick to run. Rows go to the device in blocks of chunk_rows (default: about 64 MiB)."""
-        i32 = np.int32
         w = self.shard_layout()[1]
-        hb = np.ascontiguousarray(hb, dtype=i32).reshape(self.n, w)
-        ts = np.ascontiguousarray(ts, dtype=i32).reshape(self.n, w)
-        hbt = np.ascontiguousarray(heartbeat, dtype=i32).reshape(self.n)
-        fl = np.ascontiguousarray(failed, dtype=i32).reshape(self.n)
-        tg = np.ascontiguousarray(targets, dtype=i32).reshape(self.n, 5)
-        cnt = np.ascontiguousarray(counts, dtype=i32).reshape(self.n)
-        if chunk_rows is None:
-            chunk_rows = max(1, (64 << 20) // (8 * w))
-        self._call("gm_load_begin", self.h, int(t))
-        for r0 in range(0, self.n, chunk_rows):
-            m = min(chunk_rows, self.n - r0)
-            self._call("gm_load_rows", self.h, r0, m, _ptr(hb[r0:r0 + m]), _ptr(ts[r0:r0 + m]))
-        self._call("gm_load_commit", self.h, _ptr(hbt), _ptr(fl), _ptr(tg), _ptr(cnt))
+        hb = np.ascontiguousarray(hb, dtype=np.int32).reshape(self.n, w)
+        ts = np.ascontiguousarray(ts, dtype=np.int32).reshape(self.n, w)
+        self._load(("gm_load_begin", "gm_load_rows", "gm_load_commit"), t, 0, (hb, ts), chunk_rows,
+                   heartbeat, failed, targets, counts)
 
     def load_stats(self):
         """{"rows", "staging_bytes", "check_ms", "encode_ms"} of the last load (kernel times only
         while set_timing is on)"""
-        v = (ctypes.c_double * 4)()
-        self._call("gm_load_stats", self.h, v)
-        return {"rows": int(v[0]), "staging_bytes": int(v[1]), "check_ms": float(v[2]), "encode_ms": float(v[3])}
+        return self._stage_stats("gm_load_stats", ("check_ms", "encode_ms"))
 
     def load_views(self, t, views, heartbeat, failed, targets, counts, chunk_rows=None):
         """PARTIAL: replace the whole state between two ticks (gm_load_views_begin / gm_load_views /
@@ -442,31 +449,18 @@ class Simulator:
         own nodes; heartbeat [nloc]; failed [n], the crash flags of the WHOLE cluster; targets
         [nloc][5] and counts [nloc] as read_targets returns them; t is the next tick to run. The
         views go to the device in blocks of chunk_rows nodes (default: about 64 MiB)."""
-        i32 = np.int32
         n0, nloc = self.shard_layout()
         v = self.cfg.view or 32
         vw = np.ascontiguousarray(views, dtype=np.uint64)  # a view of a memory-mapped array: read block by block
         if vw.shape != (nloc, v):
             raise ValueError(f"load_views: views of shape {vw.shape}, this context holds [{nloc}][{v}]")
-        hbt = np.ascontiguousarray(heartbeat, dtype=i32).reshape(nloc)
-        fl = np.ascontiguousarray(failed, dtype=i32).reshape(self.n)
-        tg = np.ascontiguousarray(targets, dtype=i32).reshape(nloc, 5)
-        cnt = np.ascontiguousarray(counts, dtype=i32).reshape(nloc)
-        if chunk_rows is None:
-            chunk_rows = max(1, (64 << 20) // (8 * v))
-        self._call("gm_load_views_begin", self.h, int(t))
-        for r0 in range(0, nloc, chunk_rows):
-            m = min(chunk_rows, nloc - r0)
-            blk = np.ascontiguousarray(vw[r0:r0 + m], dtype=np.uint64)
-            self._call("gm_load_views", self.h, n0 + r0, m, _ptr(blk, ctypes.c_uint64))
-        self._call("gm_load_views_commit", self.h, _ptr(hbt), _ptr(fl), _ptr(tg), _ptr(cnt))
+        self._load(("gm_load_views_begin", "gm_load_views", "gm_load_views_commit"), t, n0, (vw,), chunk_rows,
+                   heartbeat, failed, targets, counts)
 
     def load_views_stats(self):
         """{"rows", "staging_bytes", "check_ms", "store_ms"} of the last view load (kernel times only
         while set_timing is on)"""
-        v = (ctypes.c_double * 4)()
-        self._call("gm_load_views_stats", self.h, v)
-        return {"rows": int(v[0]), "staging_bytes": int(v[1]), "check_ms": float(v[2]), "store_ms": float(v[3])}
+        return self._stage_stats("gm_load_views_stats", ("check_ms", "store_ms"))
 
     def dump_tables(self):
         n = ctypes.c_size_t()

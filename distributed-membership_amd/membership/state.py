@@ -24,13 +24,15 @@ import os
 
 import numpy as np
 
+from .abi import default_chunk_rows
+
 KEYS = ("t", "hb", "ts", "heartbeat", "failed", "targets", "counts")
 NODE_KEYS = ("t", "heartbeat", "failed", "targets", "counts")  # everything but the tables (save_dir's nodes.npz)
 
 
-def _chunk_rows(w, chunk_rows):
-    """rows per block: as given, else about 64 MiB of (hb, ts) (Simulator.load_state's default)"""
-    return max(1, int(chunk_rows)) if chunk_rows is not None else max(1, (64 << 20) // (8 * w))
+def _chunk_rows(width, chunk_rows):
+    """rows per block: as given, else about 64 MiB of (hb, ts) or views (the loads' default)"""
+    return max(1, int(chunk_rows)) if chunk_rows is not None else default_chunk_rows(width)
 
 
 def _read_blocks(sim, hb, ts, chunk_rows):
@@ -45,10 +47,44 @@ def _read_blocks(sim, hb, ts, chunk_rows):
         ts[r0:r0 + k] = bt
 
 
-def _nodes(sim):
+def _nodes(sim, view=False, failed=None):
+    """Everything of a snapshot but the tables. view: of a PARTIAL context (a view snapshot) -- with n0,
+    and `failed` the flags of the whole cluster: the caller's (default 0), this context's own nodes' read."""
     st = sim.read_nodes()
     tg, cnt = sim.read_targets()
-    return {"t": int(sim.time), "heartbeat": st[:, 3].copy(), "failed": st[:, 2].copy(), "targets": tg, "counts": cnt}
+    out = {"t": int(sim.time), "heartbeat": st[:, 3].copy(), "failed": st[:, 2].copy(), "targets": tg, "counts": cnt}
+    if view:
+        n0, nloc = sim.shard_layout()
+        cluster = np.zeros(sim.n, dtype=np.int32) if failed is None else np.array(failed, dtype=np.int32).reshape(sim.n)
+        cluster[n0:n0 + nloc] = out["failed"]
+        out.update(n0=n0, failed=cluster)
+    return out
+
+
+def _save_dir(path, names, dtype, shape, fill, nodes, keys):
+    """The directory form of a state: the tables `names` (.npy, dtype [rows][width] = shape, created
+    memory-mapped and written by fill(*tables)) and nodes.npz (the `keys` of `nodes`, int32)."""
+    os.makedirs(path, exist_ok=True)
+    tables = [np.lib.format.open_memmap(os.path.join(path, name + ".npy"), mode="w+", dtype=dtype, shape=shape)
+              for name in names]
+    fill(*tables)
+    for a in tables:
+        a.flush()
+    del tables
+    with open(os.path.join(path, "nodes.npz"), "wb") as f:
+        np.savez(f, **{k: np.asarray(nodes[k], dtype=np.int32) for k in keys})
+
+
+def _load_dir(path, names, keys):
+    """What _save_dir wrote as a snapshot: the tables memory-mapped read-only, t and n0 as int."""
+    with np.load(os.path.join(path, "nodes.npz")) as z:
+        missing = [k for k in keys if k not in z.files]
+        if missing:
+            raise ValueError(f"{path}: nodes.npz lacks {missing}")
+        snap = {k: int(z[k]) if k in ("t", "n0") else z[k].copy() for k in keys}
+    for name in names:
+        snap[name] = np.load(os.path.join(path, name + ".npy"), mmap_mode="r")
+    return snap
 
 
 def snapshot(sim, device=False, chunk_rows=None):
@@ -87,27 +123,13 @@ def save_dir(sim, path, chunk_rows=None):
     """Stream the state of a SCALED context to the directory `path`: hb.npy / ts.npy (int32 [n][w], written
     block by block through read_rows, chunk_rows rows at a time) and nodes.npz (t, heartbeat, failed,
     targets, counts)."""
-    os.makedirs(path, exist_ok=True)
-    w = sim.shard_layout()[1]
-    planes = [np.lib.format.open_memmap(os.path.join(path, name), mode="w+", dtype=np.int32, shape=(sim.n, w))
-              for name in ("hb.npy", "ts.npy")]
-    _read_blocks(sim, planes[0], planes[1], chunk_rows)
-    for p in planes:
-        p.flush()
-    del planes
-    nodes = _nodes(sim)
-    with open(os.path.join(path, "nodes.npz"), "wb") as f:
-        np.savez(f, **{k: np.asarray(nodes[k], dtype=np.int32) for k in NODE_KEYS})
+    _save_dir(path, ("hb", "ts"), np.int32, (sim.n, sim.shard_layout()[1]),
+              lambda hb, ts: _read_blocks(sim, hb, ts, chunk_rows), _nodes(sim), NODE_KEYS)
 
 
 def load_dir(path):
     """The snapshot save_dir wrote, hb / ts memory-mapped read-only (restore loads them block by block)."""
-    with np.load(os.path.join(path, "nodes.npz")) as z:
-        snap = {k: z[k].copy() for k in NODE_KEYS}
-    snap["t"] = int(snap["t"])
-    snap["hb"] = np.load(os.path.join(path, "hb.npy"), mmap_mode="r")
-    snap["ts"] = np.load(os.path.join(path, "ts.npy"), mmap_mode="r")
-    return snap
+    return _load_dir(path, ("hb", "ts"), NODE_KEYS)
 
 
 def slice_columns(snap, layout):
@@ -154,10 +176,6 @@ VIEW_KEYS = ("t", "n0", "views", "heartbeat", "failed", "targets", "counts")
 VIEW_NODE_KEYS = ("t", "n0", "heartbeat", "failed", "targets", "counts")  # view_save_dir's nodes.npz
 
 
-def _view_rows(v, chunk_rows):
-    return max(1, int(chunk_rows)) if chunk_rows is not None else max(1, (64 << 20) // (8 * v))
-
-
 def _check_view_snap(snap):
     missing = [k for k in VIEW_KEYS if k not in snap]
     if missing:
@@ -175,23 +193,11 @@ def _check_view_snap(snap):
     return n0, nloc, n
 
 
-def _view_nodes(sim, failed=None):
-    n0, nloc = sim.shard_layout()
-    st = sim.read_nodes()
-    tg, cnt = sim.read_targets()
-    if failed is None:
-        failed = np.zeros(sim.n, dtype=np.int32)
-    else:
-        failed = np.array(failed, dtype=np.int32).reshape(sim.n)
-    failed[n0:n0 + nloc] = st[:, 2]
-    return {"t": int(sim.time), "n0": n0, "heartbeat": st[:, 3].copy(), "failed": failed, "targets": tg, "counts": cnt}
-
-
 def view_snapshot(sim, failed=None):
     """The state of a PARTIAL context between two ticks (a row shard: its own nodes). failed: the crash
     flags of the whole cluster for a row shard's snapshot (its own nodes' flags are read from it)."""
     n0, nloc = sim.shard_layout()
-    return dict(_view_nodes(sim, failed), views=sim.read_views(n0, nloc))
+    return dict(_nodes(sim, True, failed), views=sim.read_views(n0, nloc))
 
 
 def view_restore(sim, snap, chunk_rows=None):
@@ -238,29 +244,19 @@ def join_rows(snaps):
 def view_save_dir(sim, path, chunk_rows=None, failed=None):
     """Stream the state of a PARTIAL context to the directory `path`: views.npy (uint64 [nloc][V], written
     block by block through read_views, chunk_rows nodes at a time) and nodes.npz (the other keys)."""
-    os.makedirs(path, exist_ok=True)
     n0, nloc = sim.shard_layout()
     v = sim.cfg.view or 32
-    views = np.lib.format.open_memmap(os.path.join(path, "views.npy"), mode="w+", dtype=np.uint64, shape=(nloc, v))
-    m = min(nloc, _view_rows(v, chunk_rows))
-    for r0 in range(0, nloc, m):
-        k = min(m, nloc - r0)
-        views[r0:r0 + k] = sim.read_views(n0 + r0, k)
-    views.flush()
-    del views
-    nodes = _view_nodes(sim, failed)
-    with open(os.path.join(path, "nodes.npz"), "wb") as f:
-        np.savez(f, **{k: np.asarray(nodes[k], dtype=np.int32) for k in VIEW_NODE_KEYS})
+
+    def fill(views):
+        m = min(nloc, _chunk_rows(v, chunk_rows))
+        for r0 in range(0, nloc, m):
+            k = min(m, nloc - r0)
+            views[r0:r0 + k] = sim.read_views(n0 + r0, k)
+    _save_dir(path, ("views",), np.uint64, (nloc, v), fill, _nodes(sim, True, failed), VIEW_NODE_KEYS)
 
 
 def view_load_dir(path):
     """The snapshot view_save_dir wrote, views memory-mapped read-only (view_restore loads them block by block)."""
-    with np.load(os.path.join(path, "nodes.npz")) as z:
-        missing = [k for k in VIEW_NODE_KEYS if k not in z.files]
-        if missing:
-            raise ValueError(f"{path}: nodes.npz lacks {missing}")
-        snap = {k: z[k].copy() for k in VIEW_NODE_KEYS}
-    snap["t"], snap["n0"] = int(snap["t"]), int(snap["n0"])
-    snap["views"] = np.load(os.path.join(path, "views.npy"), mmap_mode="r")
+    snap = _load_dir(path, ("views",), VIEW_NODE_KEYS)
     _check_view_snap(snap)
     return snap

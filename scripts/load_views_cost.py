@@ -88,7 +88,7 @@ def main():
             m = min(block, n - r0)
             src._call("gm_read_views", src.h, r0, m, views[r0:r0 + m].ctypes.data_as(u64p))
     _, read_inplace_ms = ms(read_all_inplace)
-    nodes, nodes_ms = ms(lambda: state._view_nodes(src))
+    nodes, nodes_ms = ms(lambda: state._nodes(src, view=True))
     snap = dict(nodes, views=views)
 
     dst = make(a)

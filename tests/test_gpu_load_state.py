@@ -428,3 +428,38 @@ def test_clean_load_after_a_failed_one_continues_against_the_oracle():
     state.restore(sim, snap)
     assert same_state(sim, ora)
     _continue(sim, ora, 3)
+
+
+# ---- 10. the timed branches of the block loop
+def test_timed_load_equals_untimed_load(monkeypatch):
+    """gm_set_timing changes what a load measures, not what it writes: the same state through launches of
+    7 rows into a timed and an untimed context, then 3 ticks on both"""
+    ora, kw = _state300(0)
+    snap = _oracle_snapshot(ora)
+    _check_state300(snap)
+    monkeypatch.setenv("GM_LOAD_STAGE_ROWS", "7")
+    timed, plain = (Simulator(300, GM_MODE_SCALED, band=64, **kw) for _ in range(2))
+    timed.set_timing(True)
+    for sim in (timed, plain):
+        state.restore(sim, snap)
+    st, sp = timed.load_stats(), plain.load_stats()
+    assert st["rows"] == 300 and sp["rows"] == 300
+    assert st["staging_bytes"] == sp["staging_bytes"]
+    assert st["check_ms"] > 0 and st["encode_ms"] > 0
+    assert sp["check_ms"] == 0 and sp["encode_ms"] == 0
+
+    def same(what):
+        for a, b in zip(timed.read_table(), plain.read_table()):
+            assert np.array_equal(a, b), f"tables differ {what}"
+        assert np.array_equal(timed.read_nodes(), plain.read_nodes()), f"node state differs {what}"
+        for a, b in zip(timed.read_targets(), plain.read_targets()):
+            assert np.array_equal(a, b), f"targets differ {what}"
+        assert timed.dump_tables() == plain.dump_tables(), f"dumps differ {what}"
+
+    same("after the load")
+    assert plain.dump_tables() == ora.dump()
+    for _ in range(3):
+        timed.tick()
+        plain.tick()
+    assert timed.dump_tables() == plain.dump_tables(), "dumps differ after 3 ticks"
+    assert timed.tick_stats()["err"] == 0 and plain.tick_stats()["err"] == 0

@@ -517,3 +517,52 @@ def test_contract_group_with_one_member_not_loaded(base, monkeypatch):
         with pytest.raises(GmError) as e:
             s.tick()
         assert e.value.code == ESTATE
+
+
+# ------------------------------------------------------------------ 7. the timed branches of the block loop
+def test_timed_load_equals_untimed_load(base, monkeypatch):
+    """gm_set_timing changes what a load measures, not what it writes: the same state through launches of
+    7 nodes into a timed and an untimed context, and into a third, timed one whose first load a bad block
+    voided: the begin of its clean load resets the times. Then 3 ticks on all three."""
+    good, _ = base
+    n, v = 300, 32
+    monkeypatch.setenv("GM_LOAD_STAGE_ROWS", "7")
+    timed, plain, again = (make(n, v)[0] for _ in range(3))
+    timed.set_timing(True)
+    again.set_timing(True)
+    for sim in (timed, plain):
+        state.view_restore(sim, good)
+    # a gap in the view of a node 22 launches into the one block: the launches before it pass and are timed
+    bad = copy.deepcopy(good)
+    i = live_node(bad, 150)
+    bad["views"][i, other_slot(bad, i)] = 0
+    with pytest.raises(GmError) as e:
+        state.view_restore(again, bad)
+    assert e.value.code == EINVAL and str(e.value).startswith("gm_load_views:")
+    sv = again.load_views_stats()
+    assert i >= 7 and sv["rows"] == i // 7 * 7 and sv["check_ms"] > 0 and sv["store_ms"] > 0
+    again._call("gm_load_views_begin", again.h, good["t"])
+    s0 = again.load_views_stats()
+    assert s0["rows"] == 0 and s0["check_ms"] == 0 and s0["store_ms"] == 0  # only the clean load counts
+    assert s0["staging_bytes"] == sv["staging_bytes"]
+    again._call("gm_load_views", again.h, 0, n, good["views"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+    arrs = [np.ascontiguousarray(good[k], dtype=np.int32) for k in ("heartbeat", "failed", "targets", "counts")]
+    again._call("gm_load_views_commit", again.h, *[a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) for a in arrs])
+    st, sp, sa = timed.load_views_stats(), plain.load_views_stats(), again.load_views_stats()
+    assert st["rows"] == n and sp["rows"] == n and sa["rows"] == n
+    assert st["staging_bytes"] == sp["staging_bytes"] == sa["staging_bytes"]
+    assert st["check_ms"] > 0 and st["store_ms"] > 0 and sa["check_ms"] > 0 and sa["store_ms"] > 0
+    assert sp["check_ms"] == 0 and sp["store_ms"] == 0
+    for sim in (timed, again):
+        assert sim.time == plain.time == good["t"]
+        assert np.array_equal(sim.read_views(0, n), plain.read_views(0, n))
+        assert np.array_equal(sim.read_nodes(), plain.read_nodes())
+        for a, b in zip(sim.read_targets(), plain.read_targets()):
+            assert np.array_equal(a, b)
+        assert sim.dump_tables() == plain.dump_tables()
+    assert np.array_equal(plain.read_views(0, n), good["views"])
+    for _ in range(3):
+        for sim in (timed, plain, again):
+            sim.tick()
+    assert timed.dump_tables() == plain.dump_tables() == again.dump_tables(), "dumps differ after 3 ticks"
+    assert all(s.tick_stats()["err"] == 0 for s in (timed, plain, again))
