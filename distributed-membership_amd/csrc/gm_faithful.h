@@ -67,3 +67,22 @@ __global__ void gm_f_sendprep(FState s);
 __global__ void gm_f_s1expand(FState s);
 __global__ void gm_f_sendscan(FState s, int t);
 __global__ void gm_f_sendemit(FState s);
+
+// One member of a batch (gm_batch_tick): its state and time as of the last slot upload, the buffers
+// in the order the tick starts with, drop_pct_now filled in.
+struct FBSlot {
+  FState f;
+  int t;
+  int pad;
+};
+
+// The same tick for R independent clusters in one launch each (launched by gm_host_batch.hip):
+// blockIdx.y is the member, grid x what the largest member needs. `step` = batch ticks since the
+// slots were uploaded: the member's time is slot.t + step and its buffers have swapped step times.
+__global__ void gm_fb_recv(const FBSlot *slots, int step);
+__global__ void gm_fb_recvout(const FBSlot *slots, int step);
+__global__ void gm_fb_node(const FBSlot *slots, int step);
+__global__ void gm_fb_sendprep(const FBSlot *slots, int step);
+__global__ void gm_fb_s1expand(const FBSlot *slots, int step);
+__global__ void gm_fb_sendscan(const FBSlot *slots, int step);
+__global__ void gm_fb_sendemit(const FBSlot *slots, int step);

@@ -3,6 +3,7 @@
 //
 //   gm_host.hip           create / destroy, gm_tick and the small calls, timing ring, error latching
 //   gm_host_faithful.hip  FAITHFUL: state, tick, mailbox collection
+//   gm_host_batch.hip     FAITHFUL: R contexts ticked together (gm_batch_*)
 //   gm_host_scaled.hip    SCALED: state, the single-context tick
 //   gm_host_shard.hip     SCALED column shards: RCCL attach, phase API, the sharded tick, loopback
 //   gm_host_partial.hip   PARTIAL: state, tick, the row shards' exchange
@@ -117,9 +118,31 @@ struct gm_shard_exchange {
   hipEvent_t done = nullptr;         // the tick's exchange and what follows it are done (exchange stream)
 };
 
+// R FAITHFUL contexts of one device ticked together (gm_batch_*, gm_host_batch.hip). While a context
+// is a member its `stream` is the batch's, so every call on a member and every batch tick are
+// ordered by construction. The device slots hold every member's FState as of the last upload;
+// the kernels derive time and buffer order from the batch ticks since (FBSlot, gm_faithful.h), so
+// a slot is uploaded again only when its member changed other than by the batch's own tick.
+#define GM_BATCH_RING 4
+struct gm_batch {
+  std::vector<gm_ctx *> m;           // the members
+  std::vector<hipStream_t> own;      // their own streams, given back by gm_batch_destroy
+  hipStream_t stream = nullptr;
+  FBSlot *slots = nullptr;           // device [R]
+  std::vector<FBSlot> cur;           // what the device slots hold
+  int step = 0;                      // batch ticks since the slots were uploaded (-1: never uploaded)
+  FBSlot *ring[GM_BATCH_RING] = {nullptr, nullptr, nullptr, nullptr};  // pinned [R] each: the uploads' sources
+  hipEvent_t ring_ev[GM_BATCH_RING] = {nullptr, nullptr, nullptr, nullptr};  // the upload from that buffer is done
+  int uploads = 0;
+  int gx_node = 0, gx_s1 = 0, gx_emit = 0;  // grid x of the kernels that size it from n: the largest member's
+  size_t smem = 0;                   // gm_fb_node's dynamic LDS: the largest member's
+  std::vector<int> due;              // scratch: members whose mailbox this tick collects
+};
+
 struct gm_ctx {
   gm_config cfg;
   hipStream_t stream = nullptr;
+  gm_batch *batch = nullptr;         // FAITHFUL: the batch this context belongs to (stream is then the batch's)
   int dmax = 0;                      // status exchange depth (sharded)
   ncclComm_t comm = nullptr;         // RCCL communicator across column shards
   hipEvent_t k0 = nullptr, k1 = nullptr;  // per-tick band-kernel events (sharded)
@@ -257,7 +280,14 @@ static inline int xchunk_rows(const SState &s, int ch) {  // real rows of exchan
 int create_faithful(gm_ctx *c);
 void destroy_faithful(gm_ctx *c);
 int f_collect(gm_ctx *c);
+int f_collect_enqueue(gm_ctx *c, bool *enqueued);
+int f_collect_parse(gm_ctx *c);
+int f_tick_check(const gm_ctx *c, bool *collect);
+FState f_tick_begin(gm_ctx *c);
 int tick_faithful(gm_ctx *c);
+// grid x of the two FAITHFUL kernels sized from the draw capacity (grid-stride: any size computes the same)
+static inline int f_s1expand_blocks(const FState &f) { return std::min(1024, (f.draw_cap / 31 + 1 + 7) / 8); }
+static inline int f_sendemit_blocks(const FState &f) { return std::min(1024, (f.draw_cap + 255) / 256); }
 
 // gm_host_scaled.hip
 int create_scaled(gm_ctx *c);

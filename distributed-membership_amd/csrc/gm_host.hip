@@ -112,6 +112,7 @@ int gmh::exchange_create(gm_ctx *c, int chunks) {
 // feature and mode then frees what it created outside `allocs`.
 extern "C" int gm_destroy(gm_ctx *c) {
   if (!c) return GM_EINVAL;
+  if (c->batch) return GM_ESTATE;  // gm_batch_destroy first: the batch's slots point into this context
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->ph.side) (void)hipStreamSynchronize(c->ph.side);  // the S2 prefetch of tick t+1 may still be writing
   if (c->xch.stream) (void)hipStreamSynchronize(c->xch.stream);

@@ -159,16 +159,22 @@ static void detect_host(gm_ctx *c, int t, int kind, int subject) {
   }
 }
 
-// Collect the mailbox of every tick enqueued since the last collection: one copy of the
-// count, the error flags and the first GM_F_MAILBOX records (more: a second copy), one
-// wait; the records are staged to `pending` in the reference's order, the count reset in
-// stream order.
-int gmh::f_collect(gm_ctx *c) {
-  if (c->fh.inflight == 0) return c->latched;
-  c->fh.inflight = 0;
+// Collect the mailbox of every tick enqueued since the last collection, in two halves so that a
+// batch collects several members with one wait between them. f_collect_enqueue: one copy of the
+// count, the error flags and the first GM_F_MAILBOX records on the context's stream (false:
+// nothing enqueued since the last collection). After the stream was waited for, f_collect_parse
+// stages the records to `pending` in the reference's order (more than GM_F_MAILBOX: a second copy)
+// and resets the count in stream order.
+int gmh::f_collect_enqueue(gm_ctx *c, bool *enqueued) {
+  *enqueued = c->fh.inflight != 0;
+  if (!*enqueued) return GM_OK;
   HIPCHECK(hipMemcpyAsync(c->fh.mail, c->f.ev_count, 16 + sizeof(FEvent) * GM_F_MAILBOX, hipMemcpyDeviceToHost,
                           c->stream));
-  HIPCHECK(hipStreamSynchronize(c->stream));
+  return GM_OK;
+}
+
+int gmh::f_collect_parse(gm_ctx *c) {
+  c->fh.inflight = 0;
   const unsigned long long nev = *(const unsigned long long *)c->fh.mail;
   const uint32_t e = *(const uint32_t *)((const uint8_t *)c->fh.mail + 8);
   HIPCHECK(hipMemsetAsync(c->f.ev_count, 0, sizeof(unsigned long long), c->stream));
@@ -194,33 +200,63 @@ int gmh::f_collect(gm_ctx *c) {
   return c->latched;
 }
 
+int gmh::f_collect(gm_ctx *c) {
+  bool enq = false;
+  TRY(f_collect_enqueue(c, &enq));
+  if (!enq) return c->latched;
+  HIPCHECK(hipStreamSynchronize(c->stream));
+  return f_collect_parse(c);
+}
+
+// The host part of one member's FAITHFUL tick, shared by gm_tick and gm_batch_tick, in two steps so
+// that a batch can check every member before it changes any. f_tick_check: the time limit, and
+// whether the mailbox must be collected before this tick is enqueued -- the record buffer could
+// fill, or nodeStart resets a crash flag the recorder still reads.
+int gmh::f_tick_check(const gm_ctx *c, bool *collect) {
+  if (c->t >= F_MAX_TIME) return GM_ERANGE;  // EmulNet.cpp:109 assert(time < MAX_TIME)
+  *collect = (c->fh.inflight + 1) * f_tick_event_bound(c) > c->f.ev_cap;
+  if (c->det.tmax && c->nfailed)  // the recorder reads failed_h as the enqueued ticks saw it
+    for (int i = 0; i < c->n; i++) *collect |= (int)(0.25 * i) == c->t && c->failed_h[i];
+  return GM_OK;
+}
+
+// f_tick_begin (after the collection, if one was due): nodeStart of this tick's starters resets
+// bFailed on the device (MP1Node.cpp:108-116), mirrored here; the tick is counted as enqueued.
+// Returns the state the tick's kernels get up to gm_f_recvout, drop_pct_now filled in; the rest get
+// it with buf / buf2 and bkey / bkey2 swapped (gm_f_recvout compacts the survivors into buf2),
+// which is what c->f holds afterwards.
+FState gmh::f_tick_begin(gm_ctx *c) {
+  if (c->nfailed)
+    for (int i = 0; i < c->n; i++)
+      if ((int)(0.25 * i) == c->t && c->failed_h[i]) {
+        c->failed_h[i] = 0;
+        c->fail_t[i] = 0x7FFFFFFF;
+        c->nfailed--;
+      }
+  FState st = c->f;
+  st.drop_pct_now = c->dropmsg ? (int)(c->cfg.drop_prob * 100) : -1;  // EmulNet.cpp:92
+  std::swap(c->f.buf, c->f.buf2);
+  std::swap(c->f.bkey, c->f.bkey2);
+  c->fh.inflight++;
+  return st;
+}
+
 // FAITHFUL ticks are enqueued without a host wait: the records stay on the device until a
 // call needs them (f_settle) or the next tick could overflow the record buffer.
 int gmh::tick_faithful(gm_ctx *c) {
-  if (c->t >= F_MAX_TIME) return GM_ERANGE;  // EmulNet.cpp:109 assert(time < MAX_TIME)
-  if ((c->fh.inflight + 1) * f_tick_event_bound(c) > c->f.ev_cap) TRY(f_collect(c));
-  // nodeStart of this tick's starters resets bFailed on the device (MP1Node.cpp:108-116); mirror it
-  for (int i = 0; i < c->n; i++)
-    if ((int)(0.25 * i) == c->t && c->failed_h[i]) {
-      if (c->det.tmax) TRY(f_collect(c));  // the recorder reads failed_h as the enqueued ticks saw it
-      c->failed_h[i] = 0;
-      c->fail_t[i] = 0x7FFFFFFF;
-      c->nfailed--;
-    }
-  FState st = c->f;
+  bool collect = false;
+  TRY(f_tick_check(c, &collect));
+  if (collect) TRY(f_collect(c));
+  FState st = f_tick_begin(c);
   hipLaunchKernelGGL(gm_f_recv, dim3(1), dim3(1024), F_RECV_LDS, c->stream, st, c->t);
   hipLaunchKernelGGL(gm_f_recvout, dim3(64), dim3(256), 0, c->stream, st, c->t);
-  std::swap(c->f.buf, c->f.buf2);  // gm_f_recvout compacted the survivors into buf2
-  std::swap(c->f.bkey, c->f.bkey2);
-  st = c->f;
-  st.drop_pct_now = c->dropmsg ? (int)(c->cfg.drop_prob * 100) : -1;  // EmulNet.cpp:92
+  std::swap(st.buf, st.buf2);
+  std::swap(st.bkey, st.bkey2);
   hipLaunchKernelGGL(gm_f_node, dim3(c->n), dim3(256), c->fh.smem, c->stream, st, c->t);
   hipLaunchKernelGGL(gm_f_sendprep, dim3(1), dim3(64), 0, c->stream, st);
-  const int rounds = st.draw_cap / 31 + 1;
-  hipLaunchKernelGGL(gm_f_s1expand, dim3(std::min(1024, (rounds + 7) / 8)), dim3(256), 0, c->stream, st);
+  hipLaunchKernelGGL(gm_f_s1expand, dim3(f_s1expand_blocks(st)), dim3(256), 0, c->stream, st);
   hipLaunchKernelGGL(gm_f_sendscan, dim3(1), dim3(1024), 0, c->stream, st, c->t);
-  hipLaunchKernelGGL(gm_f_sendemit, dim3(std::min(1024, (st.draw_cap + 255) / 256)), dim3(256), 0, c->stream, st);
+  hipLaunchKernelGGL(gm_f_sendemit, dim3(f_sendemit_blocks(st)), dim3(256), 0, c->stream, st);
   HIPCHECK(hipGetLastError());
-  c->fh.inflight++;
   return c->latched;
 }

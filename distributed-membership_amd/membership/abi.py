@@ -8,6 +8,7 @@ GM_ABI_VERSION = 2
 GM_MODE_FAITHFUL, GM_MODE_SCALED, GM_MODE_PARTIAL = 0, 1, 2
 GM_EV_JOINED, GM_EV_REMOVED, GM_EV_START_GROUP, GM_EV_TRY_JOIN, GM_EV_TIME_MARK = 1, 2, 3, 4, 5
 GM_OK, GM_ERANGE = 0, -4
+GM_EINVAL, GM_ESTATE, GM_EUNSUPPORTED = -1, -5, -6
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -112,6 +113,7 @@ SIGNATURES = {
     "gm_read_rows": [_ctx, _i32, _i32, _P(_i32), _P(_i32)], "gm_read_rows_stats": [_ctx, _P(_f64)],
     "gm_load_views_begin": [_ctx, _i32], "gm_load_views": [_ctx, _i32, _i32, _P(_u64)],
     "gm_load_views_commit": _load4, "gm_load_views_stats": [_ctx, _P(_f64)],
+    "gm_batch_create": [_P(_ctx), _i32, _P(_ctx)], "gm_batch_tick": [_ctx], "gm_batch_destroy": [_ctx],
 }
 EXPORTS = list(SIGNATURES) + ["gm_strerror"]  # the one entry point that returns no status
 
@@ -199,6 +201,8 @@ class Simulator:
         return rc
 
     def close(self):
+        if getattr(self, "_batch", None) is not None:
+            self._batch.close()  # a member cannot be destroyed (GM_ESTATE): its batch goes first
         if getattr(self, "h", None):
             self.lib.gm_destroy(self.h)
             self.h = None
@@ -540,6 +544,43 @@ class Simulator:
 
     def shard_end_tick(self):
         self._call("gm_shard_end_tick", self.h)
+
+
+class Batch:
+    """R FAITHFUL Simulators of one device ticked together (gm_batch_*): tick() is one tick() of every
+    member in one launch set. Every other call stays the member's own, with its usual meaning, also
+    between batch ticks. The batch keeps its members alive; close() gives them back (a member's
+    close() closes its batch first)."""
+
+    def __init__(self, sims):
+        self.lib = load_library()
+        self.sims = list(sims)
+        arr = (ctypes.c_void_p * len(self.sims))(*[s.h for s in self.sims])
+        h = ctypes.c_void_p()
+        rc = self.lib.gm_batch_create(arr, len(self.sims), ctypes.byref(h))
+        if rc != GM_OK:
+            raise GmError(rc, "gm_batch_create")
+        self.h = h
+        for s in self.sims:
+            s._batch = self
+
+    def tick(self):
+        rc = self.lib.gm_batch_tick(self.h)
+        if rc != GM_OK:
+            raise GmError(rc, "gm_batch_tick")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gm_batch_destroy(self.h)
+            self.h = None
+            for s in self.sims:
+                s._batch = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def comm_unique_id():

@@ -29,10 +29,12 @@
  *   gm_msgcount     EmulNet::sent_msgs / recv_msgs as dumped by ENcleanup (EmulNet.cpp:184-220)
  *   gm_dump_tables  Member::memberList of every node (Member.h:89-122), for parity tests
  *   gm_destroy      Application::~Application / ENcleanup storage release
+ *   gm_batch_tick   R independent Application processes, each at its own globaltime, advanced by
+ *                   one mp1Run each (the grader's three testcases, a seed ensemble)
  *
  * Conventions: every function returns GM_OK (0) or a negative GM_E* code and never
  * throws; the context owns all device memory; output buffers are caller-owned;
- * one host thread per context. gm_tick enqueues the tick on the context's HIP
+ * one host thread per context. (a batch and its members: one thread for all of them). gm_tick enqueues the tick on the context's HIP
  * stream and returns (a tick is a BSP round: sends of tick t are consumed in
  * tick t+1); every read-back function and gm_sync wait for enqueued ticks.
  */
@@ -400,6 +402,34 @@ int gm_pool_info(gm_ctx *ctx, int64_t info[4]);
  * next tick; 0 when nothing was timed. */
 int gm_set_timing(gm_ctx *ctx, int32_t on);
 int gm_last_kernel_ms(gm_ctx *ctx, float *ms);
+
+/* ---- FAITHFUL batches: R contexts of one device ticked together. The seam is R independent
+ * Application processes (Application.cpp:27-202 run R times: the grader's three testcases, the seed
+ * pairs of an ensemble): the members share nothing and may differ in n, seeds, conf values, dropmsg
+ * state, crash sets, globaltime and whether they record detection. A batch tick is the same seven
+ * launches as gm_tick's with the member as a second grid dimension, so R clusters cost about the
+ * launch latency of one.
+ * gm_batch_create: waits once for what each member has enqueued; from then until gm_batch_destroy the
+ * members run on the batch's stream, so every call on a member (gm_tick, gm_rand, gm_set_failed,
+ * gm_set_dropmsg, gm_drain_events, gm_msgcount, gm_dump_tables, gm_read_*, gm_detect*, gm_event_*,
+ * gm_sync, gm_time) keeps its meaning and is ordered with the batch ticks; a gm_tick of one member
+ * between two batch ticks leaves that member one tick further than the others. One host thread drives
+ * a batch and its members. GM_EINVAL: ctxs or out NULL, R < 1 or R > 65535, a NULL member, the same
+ * context twice, members on different devices; GM_EUNSUPPORTED: a member is not FAITHFUL; GM_ESTATE: a
+ * member already belongs to a batch. gm_destroy of a member returns GM_ESTATE and destroys nothing.
+ * gm_batch_tick: one gm_tick of every member -- the same tables, records, counters and S1 stream bit
+ * for bit -- enqueued without a host wait. All or nothing: it first checks every member and collects
+ * the mailboxes that are due (a member's record buffer could fill, or the detection recorder needs
+ * the enqueued ticks before a crash flag is reset), all of them with one host wait; then either every
+ * member's tick is enqueued and every globaltime advances, or nothing is and none does. Returns the
+ * lowest-index member's latched error if a member has one, GM_ERANGE if a member is at MAX_TIME
+ * (EmulNet.h:11). gm_set_timing / gm_last_kernel_ms of a member are not fed by batch ticks.
+ * gm_batch_destroy: waits for the batch's stream and gives the members their own streams back; they
+ * live on. */
+typedef struct gm_batch gm_batch;
+int gm_batch_create(gm_ctx **ctxs, int32_t R, gm_batch **out);
+int gm_batch_tick(gm_batch *b);
+int gm_batch_destroy(gm_batch *b);
 
 /* ---- SCALED column sharding (multi-GPU). A context with shard_count = G > 1
  * owns subject columns [c0, c0 + w) of every observer row (one context per GPU).
