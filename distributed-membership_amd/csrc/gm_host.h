@@ -8,6 +8,7 @@
 //   gm_host_shard.hip     SCALED column shards: RCCL attach, phase API, the sharded tick, loopback
 //   gm_host_partial.hip   PARTIAL: state, tick, the row shards' exchange
 //   gm_host_events.hip    event drains, detection recorder, msgcount
+//   gm_host_view_detect.hip  PARTIAL detection recorder (gm_view_detect_*)
 //   gm_host_read.hip      read-backs: rows, tables, views, nodes, targets, the censuses
 //   gm_host_stage.hip     the staged block of gm_read_rows and the loads: size, timing, stats
 //   gm_host_load.hip      gm_load_*, gm_load_views_*: one block loop, one commit tail
@@ -60,6 +61,16 @@ struct gm_view_census_scratch {
   uint8_t *blob = nullptr;
   gm_view_rec *rec = nullptr;
   int64_t nfailed = -1;              // gm_ctx.nfailed when the bitmap was last built (-1: never)
+};
+
+// PARTIAL detection recorder (gm_view_detect_record; tmax 0 = off), all on the device and allocated
+// when recording starts: gm_p_view_detect adds each recorded tick's views and records
+struct gm_view_detect_state {
+  int tmax = 0;
+  gm_view_detect_rec *rec = nullptr;  // [n]: this context's observers over all subjects of the cluster
+  uint64_t *tl = nullptr;             // [tmax][GM_VIEW_DETECT_COLS]
+  uint32_t *cls = nullptr;            // the crash bitmap of the cluster as the next tick will see it (bit id - 1)
+  uint32_t *status = nullptr;         // the reducer's status word (GM_VD_E*)
 };
 
 #define GM_STAGE_BYTES (256ull << 20)  // what a staged call's rows of one launch may take on the device
@@ -188,6 +199,7 @@ struct gm_ctx {
   PState p{};  // PARTIAL
   gm_partial_host ph;
   gm_view_census_scratch vc;
+  gm_view_detect_state vdet;
   gm_load_stage vl;
   gm_shard_exchange xch;  // SCALED column shards, PARTIAL row shards
 };
@@ -233,6 +245,16 @@ static inline hipError_t ctx_memcpy2d(gm_ctx *c, void *d, size_t dpitch, const v
                                       size_t height, hipMemcpyKind k) {
   const hipError_t e = hipMemcpy2DAsync(d, dpitch, src, spitch, width, height, k, c->stream);
   return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
+}
+
+// PARTIAL: the crash set of the whole cluster as one bit per node (bit i of word i / 32: node i, id i + 1),
+// what the view census and the detection recorder test a subject against
+static inline std::vector<uint32_t> crash_bitmap(const gm_ctx *c) {
+  std::vector<uint32_t> cls(((size_t)c->n + 31) / 32, 0u);
+  if (c->nfailed)
+    for (size_t i = 0; i < (size_t)c->n; i++)
+      if (c->failed_h[i]) cls[i >> 5] |= 1u << (i & 31);
+  return cls;
 }
 
 template <class T>
@@ -313,6 +335,10 @@ int partial_caps(gm_ctx *c);
 
 // gm_host_events.hip
 int before_tick_events(gm_ctx *c);
+
+// gm_host_view_detect.hip
+int view_detect_flags(gm_ctx *c);
+int view_detect_tick(gm_ctx *c, int t, hipStream_t st);
 
 // gm_host_stage.hip
 int stage_cap(size_t budget, size_t row_bytes, size_t rows, const char *env);

@@ -267,6 +267,7 @@ extern "C" int gm_set_failed(gm_ctx *c, const int32_t *idx, int32_t n) {
   HIPCHECK(ctx_memcpy(c, dst, c->failed_h.data() + (part ? c->p.n0 : 0), sizeof(int32_t) * (part ? c->p.nloc : c->n),
                      hipMemcpyHostToDevice));
   if (part && c->ph.sharded) TRY(partial_caps(c));  // the exchange blocks follow the live nodes per shard
+  if (part) TRY(view_detect_flags(c));  // while recording: the crash bitmap the next tick's reducer reads
   return GM_OK;
 }
 

@@ -191,7 +191,7 @@ static uint32_t *vload_given(const gm_ctx *c) { return c->vl.status - ((size_t)c
 
 extern "C" int gm_load_views_begin(gm_ctx *c, int32_t t) {
   if (!c) return GM_EINVAL;
-  if (c->cfg.mode != GM_MODE_PARTIAL || c->p.mc_sent) return GM_EUNSUPPORTED;
+  if (c->cfg.mode != GM_MODE_PARTIAL || c->p.mc_sent || c->vdet.tmax) return GM_EUNSUPPORTED;
   if (t < 5 + 1 || t > GM_T_LIMIT / 2 + 1) return GM_EINVAL;  // t0 + 1 for a t0 create_partial accepts
   if (c->latched != GM_OK) return c->latched;
   const PState &p = c->p;

@@ -305,6 +305,7 @@ int gmh::tick_partial(gm_ctx **g, int G) {
   if (k0) HIPCHECK(hipEventRecord(k0, st));
   if (!L->ph.sharded) {
     HIPCHECK(gm_launch_partial_chunk(L->p, t, mt(L, par), 0, st));
+    TRY(view_detect_tick(L, t, st));  // while recording: the tick's final views and records, reduced
     if (k1) HIPCHECK(hipEventRecord(k1, st));
   } else {
     bool check = false;
@@ -332,6 +333,9 @@ int gmh::tick_partial(gm_ctx **g, int G) {
       for (int i = 0; i < G; i++) HIPCHECK(gm_launch_partial_chunk(g[i]->p, t, mt(g[i], par), q, st));
       HIPCHECK(hipEventRecord(L->xch.chunk_ev[q], st));
     }
+    // while recording: every member's reducer behind the last chunk's node kernels, on the compute
+    // stream beside the exchange (which only reads what the reducer reads)
+    for (int i = 0; i < G; i++) TRY(view_detect_tick(g[i], t, st));
     if (k1) HIPCHECK(hipEventRecord(k1, st));
     for (int q = 0; q < K; q++) {
       HIPCHECK(hipStreamWaitEvent(L->xch.stream, L->xch.chunk_ev[q], 0));

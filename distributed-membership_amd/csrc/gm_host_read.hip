@@ -420,10 +420,7 @@ extern "C" int gm_view_census(gm_ctx *c, gm_view_rec *out, uint64_t *hist, uint6
   HIPCHECK(ctx_memset(c, c->vc.blob, 0, zero_bytes));
   if (c->vc.nfailed != c->nfailed) {  // the subjects' classes: every shard is given the whole crash set.
     // PARTIAL crash flags are only ever set, so the count of set flags names the set the bitmap holds
-    std::vector<uint32_t> cls(cls_words, 0u);
-    if (c->nfailed)
-      for (size_t i = 0; i < n; i++)
-        if (c->failed_h[i]) cls[i >> 5] |= 1u << (i & 31);
+    const std::vector<uint32_t> cls = crash_bitmap(c);
     HIPCHECK(ctx_memcpy(c, d_cls, cls.data(), sizeof(uint32_t) * cls_words, hipMemcpyHostToDevice));
     c->vc.nfailed = c->nfailed;
   }

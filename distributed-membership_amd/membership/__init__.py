@@ -10,7 +10,7 @@ from .abi import (GM_EV_JOINED, GM_EV_REMOVED, GM_EV_START_GROUP, GM_EV_TIME_MAR
                   GM_MODE_FAITHFUL, GM_MODE_PARTIAL, GM_MODE_SCALED, Batch, GmError, Simulator, crash_set, lib_path,
                   load_library)
 from .app import Application, BatchApplication, Params, format_msgcount, log_addr  # noqa: F401
-from .detect import summarize  # noqa: F401
+from .detect import merge_view_detect_shards, summarize, summarize_view_detect  # noqa: F401
 from .census import merge_shards, summarize_census  # noqa: F401
 from .views import merge_view_shards, summarize_views  # noqa: F401
 from . import state  # noqa: F401

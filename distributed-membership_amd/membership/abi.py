@@ -68,6 +68,21 @@ GM_VIEW_AGES, GM_VIEW_SIZES = 32, 33
 VIEW_DTYPE = np.dtype([("hb_min", "<i4"), ("hb_max", "<i4"), ("holders", "<u4"), ("stale", "<u4"), ("hb_sum", "<u8")])
 assert VIEW_DTYPE.itemsize == ctypes.sizeof(GmViewRec) == 24
 
+class GmViewDetectRec(ctypes.Structure):
+    _fields_ = [("fail_tick", ctypes.c_int32), ("first_removed", ctypes.c_int32), ("last_removed", ctypes.c_int32),
+                ("removals", ctypes.c_uint32), ("false_removals", ctypes.c_uint32), ("last_held", ctypes.c_int32),
+                ("late_joins", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("removed_tick_sum", ctypes.c_uint64), ("held_sum", ctypes.c_uint64)]
+
+
+# gm_view_detect_rec as a NumPy structured dtype (48 bytes, the field names of include/gm_abi.h)
+GM_VIEW_DETECT_COLS = 5  # timeline columns: joins, removals, false_removals, held, late_joins
+VIEW_DETECT_DTYPE = np.dtype([("fail_tick", "<i4"), ("first_removed", "<i4"), ("last_removed", "<i4"),
+                              ("removals", "<u4"), ("false_removals", "<u4"), ("last_held", "<i4"),
+                              ("late_joins", "<u4"), ("reserved", "<u4"),
+                              ("removed_tick_sum", "<u8"), ("held_sum", "<u8")])
+assert VIEW_DETECT_DTYPE.itemsize == ctypes.sizeof(GmViewDetectRec) == 48
+
 _P = ctypes.POINTER
 _ctx, _i32, _i64, _u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
 _f64, _sz = ctypes.c_double, ctypes.c_size_t
@@ -110,6 +125,8 @@ SIGNATURES = {
     "gm_load_commit": _load4, "gm_load_stats": [_ctx, _P(_f64)],
     "gm_census": [_ctx, _P(GmCensusRec), _P(_u64)],
     "gm_view_census": [_ctx, _P(GmViewRec), _P(_u64), _P(_u64)],
+    "gm_view_detect_record": [_ctx, _i32], "gm_view_detect": [_ctx, _P(GmViewDetectRec)],
+    "gm_view_detect_timeline": [_ctx, _i32, _P(_u64)],
     "gm_read_rows": [_ctx, _i32, _i32, _P(_i32), _P(_i32)], "gm_read_rows_stats": [_ctx, _P(_f64)],
     "gm_load_views_begin": [_ctx, _i32], "gm_load_views": [_ctx, _i32, _i32, _P(_u64)],
     "gm_load_views_commit": _load4, "gm_load_views_stats": [_ctx, _P(_f64)],
@@ -347,6 +364,27 @@ class Simulator:
         self._call("gm_view_census", self.h, rec.ctypes.data_as(ctypes.POINTER(GmViewRec)) if records else None,
                    _ptr(hist, ctypes.c_uint64), _ptr(sizes, ctypes.c_uint64))
         return rec, hist, sizes
+
+    def view_detect_record(self, tmax):
+        """PARTIAL: record how crashed nodes fade from the views, from the next tick on, for ticks < tmax
+        (gm_view_detect_record)"""
+        self._call("gm_view_detect_record", self.h, tmax)
+
+    def view_detect(self):
+        """PARTIAL: one gm_view_detect_rec per subject node of the whole cluster, as a VIEW_DETECT_DTYPE
+        array of n records (fail_tick, first_removed, last_removed, removals, false_removals, last_held,
+        late_joins, removed_tick_sum, held_sum). A row shard returns the part its own observers
+        recorded (membership.merge_view_detect_shards adds the parts up)."""
+        out = np.zeros(self.n, dtype=VIEW_DETECT_DTYPE)
+        self._call("gm_view_detect", self.h, out.ctypes.data_as(ctypes.POINTER(GmViewDetectRec)))
+        return out
+
+    def view_detect_timeline(self, t):
+        """uint64 [t, 5]: joins, removals, false removals, held entries of crashed subjects, late joins
+        recorded in each tick < t (a row shard: of its own observers)"""
+        out = np.zeros((t, GM_VIEW_DETECT_COLS), dtype=np.uint64)
+        self._call("gm_view_detect_timeline", self.h, t, _ptr(out, ctypes.c_uint64))
+        return out
 
     def read_row(self, r, c0=0, length=None):
         length = self.n if length is None else length

@@ -214,7 +214,8 @@ typedef struct gm_detect_rec {      /* 32 bytes, one per subject node */
 /* Start recording from the next tick, for ticks < tmax (0 < tmax <= 32767, else GM_EINVAL); a tick
  * >= tmax is not recorded at all. May be called between any two ticks; a second call returns
  * GM_ESTATE. PARTIAL: GM_EUNSUPPORTED (views churn ~V joins per node and tick, and a removal there
- * is an eviction). While recording is off no kernel is added to a tick. */
+ * is an eviction; gm_view_detect_record is that mode's recorder). While recording is off no kernel is
+ * added to a tick. */
 int gm_detect_record(gm_ctx *ctx, int32_t tmax);
 /* One record per subject this context owns: out[n], or out[w] for a SCALED column shard over the
  * columns [c0, c0 + w) of gm_shard_layout. GM_ESTATE before gm_detect_record. */
@@ -297,8 +298,8 @@ int gm_load_stats(gm_ctx *ctx, double stats[4]);
  * gm_read_targets. The state between two ticks -- every node's final view of tick t - 1, the heartbeat
  * counters, the crash flags, the targets drawn in t - 1 -- does not depend on the layout: a state read
  * from one context loads into G row shards (each its own nodes) and the other way round. FAITHFUL /
- * SCALED contexts and contexts recording msgcount (their history for ticks < t would be missing)
- * return GM_EUNSUPPORTED.
+ * SCALED contexts and contexts recording msgcount or gm_view_detect_record (their history for ticks < t
+ * would be missing) return GM_EUNSUPPORTED.
  *
  * gm_load_views_begin settles the run so far on both streams, discards undrained events, allocates one
  * device staging buffer of at most 256 MiB (max(1, 256 MiB / 8V) views per block; GM_LOAD_STAGE_ROWS
@@ -384,6 +385,57 @@ typedef struct gm_view_rec {      /* 24 bytes, one per subject node of the CLUST
  * entry that cannot be right -- an id outside [1, n], an even heartbeat, a heartbeat above 2T - 1, an
  * age >= GM_VIEW_AGES (the sweep removes at age 20) -- : GM_ESTATE, no output written. */
 int gm_view_census(gm_ctx *ctx, gm_view_rec *out, uint64_t *hist, uint64_t *sizes);
+
+/* ---- PARTIAL: how crashed nodes fade from the views, recorded on the device. gm_detect_record stays
+ * unsupported in this mode: a full view evicts a crashed node's stale entry in favour of fresher ones
+ * long before TREMOVE, so REMOVED records are nearly absent and JOINED records are churn. What a
+ * partial-view run is asked instead -- for how long does some live node still hold a dead node's
+ * entry, how many observer-ticks of stale belief is that, does the entry still spread, how often does a
+ * starved view remove a live node -- is reduced each recorded tick from what the tick leaves on the
+ * device: its final views, the join masks over them and the removal records. The recorder holds only
+ * that: an eviction writes no record and shows as `held` fading, not as a removal.
+ *
+ * Tick t is the tick that ran (the t of its gm_event records). "Crashed in tick t" and "live observer
+ * in tick t" follow the crash flags as tick t saw them: the gm_set_failed calls made before it ran. */
+typedef struct gm_view_detect_rec {  /* 48 bytes, one per subject node of the WHOLE cluster (index = id - 1) */
+  int32_t  fail_tick;        /* as gm_detect_rec: last tick the node ran before gm_set_failed; -1 = never failed */
+  int32_t  first_removed;    /* tick of the first REMOVED record naming it; -1 = none */
+  int32_t  last_removed;     /* tick of the last one; -1 = none */
+  uint32_t removals;         /* REMOVED records naming it (TREMOVE removals; evictions are not records) */
+  uint32_t false_removals;   /* those logged in a tick during which the subject was not crashed */
+  int32_t  last_held;        /* last recorded tick at whose end a live observer's view held it while it
+                                was crashed; -1 = none. Extinction tick = last_held + 1. */
+  uint32_t late_joins;       /* JOINED records naming it, logged by live observers while it was crashed */
+  uint32_t reserved;         /* 0 */
+  uint64_t removed_tick_sum; /* as gm_detect_rec */
+  uint64_t held_sum;         /* sum over recorded ticks in which it was crashed of the live observers
+                                holding it at the end of the tick: observer-ticks of stale belief */
+} gm_view_detect_rec;
+#define GM_VIEW_DETECT_COLS 5  /* timeline columns: joins, removals, false_removals, held, late_joins */
+/* PARTIAL; FAITHFUL / SCALED: GM_EUNSUPPORTED. Start recording from the next tick, for ticks < tmax
+ * (0 < tmax <= 32767, else GM_EINVAL); a tick >= tmax is not recorded at all. May be called between any
+ * two ticks, also after gm_load_views_commit (fail_tick then follows the load's rule); a second call
+ * returns GM_ESTATE. Device memory: 48 n + 40 tmax + n / 8 bytes. While recording, one reducer kernel
+ * follows the tick's node kernels (inside the span gm_last_kernel_ms reports), gm_set_failed also
+ * refreshes the recorder's crash bitmap, and gm_load_views_begin returns GM_EUNSUPPORTED (the history
+ * for ticks before the load would be missing). While recording is off, no kernel, allocation or copy is
+ * added to a tick. Recording does not depend on gm_keep_events and does not disturb gm_drain_events:
+ * it only reads what a drain would read. */
+int gm_view_detect_record(gm_ctx *ctx, int32_t tmax);
+/* out[n], one record per subject of the cluster. A row shard reduces its own observers' views and
+ * event rows over all n subjects and returns that part; fail_tick is filled on every shard from the
+ * common crash set. The parts combine on the host (membership.merge_view_detect_shards): counts and
+ * sums add, first_removed is the minimum over the parts that have one, last_removed and last_held the
+ * maximum. GM_ESTATE before gm_view_detect_record, and when a recorded tick met a view entry or a
+ * removal record that cannot be right (an id outside [1, n], a record count past the event row). */
+int gm_view_detect(gm_ctx *ctx, gm_view_detect_rec *out);
+/* out[t][GM_VIEW_DETECT_COLS], row i for tick i < t <= tmax (t <= 0 or t > tmax: GM_EINVAL): joins =
+ * all JOINED records of the tick; removals = all REMOVED records; false_removals = those whose subject
+ * was not crashed in the tick; held = entries naming a subject crashed in the tick, in the tick's final
+ * views of the observers live in it; late_joins = the JOINED records among those held entries. A tick
+ * before recording began is all zero. A row shard reports its own observers' rows; the shards'
+ * timelines add up. GM_ESTATE as gm_view_detect. */
+int gm_view_detect_timeline(gm_ctx *ctx, int32_t t, uint64_t *out);
 
 /* Render the membership lists of every node in the parity dump format
  * ("t i inited inGroup bFailed heartbeat n id:hb:ts ...\n" per node). */

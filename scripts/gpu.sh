@@ -21,6 +21,7 @@
 #   faithful   ./Application on the three testcases + N = 70, timed -> $O/faithful_wall.txt
 #   census     scripts/census_cost.py: gm_census at S-A (cost, self-check)  -> $O/census_cost.json
 #   viewcensus scripts/view_census_cost.py: gm_view_census at S-C (cost, self-check) -> $O/view_census_cost.json
+#   viewdetect scripts/view_detect_cost.py: the PARTIAL detection recorder at S-C (cost, self-check) -> $O/view_detect_cost.json
 #   readrows   scripts/read_cost.py: gm_read_rows at S-A beside gm_read_table (cost, self-check) -> $O/read_cost.json
 #   readrows_sb scripts/read_cost.py --sb: one 128-row block at N = 262,144 -> $O/read_cost_sb.json
 #   prof_viewcensus rocprofv3 --kernel-trace --stats of gm_view_census at S-C, tick 11 -> $O/prof_viewcensus/
@@ -75,6 +76,7 @@ run_step() {
                 done ) > $O/faithful_wall.txt 2>&1 ;;
     census) timeout -k 10 420 python -u scripts/census_cost.py --out $O/census_cost.json ${CENSUS_ARGS:-} > $O/census_cost.txt 2> $O/census_cost.err ;;
     viewcensus) timeout -k 10 900 python -u scripts/view_census_cost.py --out $O/view_census_cost.json ${VIEWCENSUS_ARGS:-} > $O/view_census_cost.txt 2> $O/view_census_cost.err ;;
+    viewdetect) timeout -k 10 600 python -u scripts/view_detect_cost.py --out $O/view_detect_cost.json ${VIEWDETECT_ARGS:-} > $O/view_detect_cost.txt 2> $O/view_detect_cost.err ;;
     readrows) timeout -k 10 540 python -u scripts/read_cost.py --out $O/read_cost.json ${READROWS_ARGS:-} > $O/read_cost.txt 2> $O/read_cost.err ;;
     readrows_sb) timeout -k 10 540 python -u scripts/read_cost.py --sb --out $O/read_cost_sb.json > $O/read_cost_sb.txt 2> $O/read_cost_sb.err ;;
     prof_viewcensus) timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_viewcensus -o vc -- \
