@@ -67,12 +67,13 @@ uint32_t oc_rd_seed(uint64_t rd_seed, int32_t tick, int32_t id) {
   return (uint32_t)mix64(z + 0x9E3779B97F4A7C15ULL);
 }
 
-typedef struct mt { uint32_t x[624]; int i; } mt;
+typedef struct mt { uint32_t x[624]; int i; int used; /* outputs taken so far (telemetry) */ } mt;
 
 static void mt_seed(mt *m, uint32_t s) {
   m->x[0] = s;
   for (int i = 1; i < 624; i++) m->x[i] = 1812433253u * (m->x[i - 1] ^ (m->x[i - 1] >> 30)) + (uint32_t)i;
   m->i = 624;
+  m->used = 0;
 }
 
 static uint32_t mt_next(mt *m) {
@@ -84,6 +85,7 @@ static uint32_t mt_next(mt *m) {
     m->i = 0;
   }
   uint32_t y = m->x[m->i++];
+  m->used++;
   y ^= y >> 11;
   y ^= (y << 7) & 0x9d2c5680u;
   y ^= (y << 15) & 0xefc60000u;
@@ -986,6 +988,8 @@ struct op_ctx {
   int ccap;
   /* msgcount analogue of the last tick: entries put on the wire / received after loss */
   int32_t *mc_sent, *mc_recv;
+  /* test telemetry of the last tick, [n][OP_PROF_WORDS] (op_last_profile); never read by a tick */
+  int32_t *prof;
 };
 
 static void op_emit(op_ctx *c, int logger, int kind, int32_t subject) {
@@ -1056,6 +1060,8 @@ op_ctx *op_create(const op_config *cfg) {
   c->rcv_src = (int32_t *)calloc((size_t)n * FANOUT + 1, sizeof(int32_t));
   c->mc_sent = (int32_t *)calloc((size_t)n, sizeof(int32_t));
   c->mc_recv = (int32_t *)calloc((size_t)n, sizeof(int32_t));
+  c->prof = (int32_t *)malloc(sizeof(int32_t) * (size_t)n * OP_PROF_WORDS);
+  memset(c->prof, 0xFF, sizeof(int32_t) * (size_t)n * OP_PROF_WORDS);
   return c;
 }
 
@@ -1072,6 +1078,7 @@ void op_destroy(op_ctx *c) {
   free(c->cid); free(c->chb); free(c->cown);
   free(c->rcv_off); free(c->rcv_src);
   free(c->mc_sent); free(c->mc_recv);
+  free(c->prof);
   free(c);
 }
 
@@ -1096,6 +1103,7 @@ static int pc_idown_cmp(const void *x, const void *y) { /* id asc, then hb desc 
 static void op_node(op_ctx *c, int i, pcand *m) {
   const int t = c->t, V = c->V;
   pnode *p = &c->nd[i];
+  int32_t *pf = c->prof + (size_t)i * OP_PROF_WORDS;
   int cnt = 0;
   for (int k = 0; k < p->cnt; k++) { m[cnt].id = p->ids[k]; m[cnt].hb = p->hbs[k]; m[cnt].own = 1; cnt++; }
   /* lists delivered to i: every sender that targeted i at t-1 (BSP, order-free for the table) */
@@ -1125,6 +1133,8 @@ static void op_node(op_ctx *c, int i, pcand *m) {
     }
     cnt = w;
   }
+  pf[OP_PROF_LISTS] = nrcv;
+  pf[OP_PROF_UNION] = cnt;
   /* self bump (heartbeat++; myPos->setheartbeat(heartbeat++)) */
   int selfk = -1;
   for (int k = 0; k < cnt; k++) if (m[k].id == i + 1) selfk = k;
@@ -1133,21 +1143,42 @@ static void op_node(op_ctx *c, int i, pcand *m) {
   m[selfk].hb = p->hbctr++;
   m[selfk].own = 2;
   /* sweep */
-  int removed = 0, w = 0;
+  int removed = 0, nremev = 0, w = 0;
   for (int k = 0; k < cnt; k++) {
     int age = t - (m[k].hb + 1) / 2;
     if (age >= TREMOVE) {
       removed++;
-      if (m[k].own) op_emit(c, i, OC_EV_REMOVE, m[k].id);
+      if (m[k].own) { op_emit(c, i, OC_EV_REMOVE, m[k].id); nremev++; }
       continue;
     }
     m[w++] = m[k];
   }
   cnt = w;
+  pf[OP_PROF_REMOVED] = removed;
+  pf[OP_PROF_REMOVE_EVENTS] = nremev;
+  pf[OP_PROF_SWEPT] = cnt;
+  pf[OP_PROF_EVICTED] = cnt > V;
+  pf[OP_PROF_CLASS_SIZE] = pf[OP_PROF_CLASS_TAKEN] = pf[OP_PROF_GROUP_SIZE] = pf[OP_PROF_GROUP_TAKEN] = 0;
+  pf[OP_PROF_CLASS_ORDINAL] = 0;
   /* evict to V */
   if (cnt > V) {
     for (int k = 0; k < cnt; k++) m[k].key = op_evict_key(c->cfg.view_seed, t, i, m[k].id);
     qsort(m, (size_t)cnt, sizeof(pcand), pc_evict_cmp);
+    { /* telemetry: the heartbeat class and the key group key >> 26 of the last entry kept (m[0] is self) */
+      const int32_t chb = m[V - 1].hb;
+      const uint64_t grp = m[V - 1].key >> 26;
+      int32_t above = 0, last = -1;
+      for (int k = 1; k < cnt; k++) {
+        if (m[k].hb > chb && m[k].hb != last) { above++; last = m[k].hb; } /* sorted: hb descending */
+        if (m[k].hb != chb) continue;
+        pf[OP_PROF_CLASS_SIZE]++;
+        pf[OP_PROF_CLASS_TAKEN] += k < V;
+        if (m[k].key >> 26 != grp) continue;
+        pf[OP_PROF_GROUP_SIZE]++;
+        pf[OP_PROF_GROUP_TAKEN] += k < V;
+      }
+      pf[OP_PROF_CLASS_ORDINAL] = above;
+    }
     cnt = V;
   }
   qsort(m, (size_t)cnt, sizeof(pcand), pc_id_cmp);
@@ -1161,6 +1192,10 @@ static void op_node(op_ctx *c, int i, pcand *m) {
   /* gossip draw (MP1Node.cpp:449-489) over the final list in id order */
   int numpot = cnt - 1 - nfail, ng = 0;
   int32_t g[FANOUT];
+  pf[OP_PROF_NUMPOT] = numpot;
+  pf[OP_PROF_STALE] = nfail - removed;
+  pf[OP_PROF_SIZE] = cnt;
+  pf[OP_PROF_DRAWS] = 0;
   if (numpot > 0) {
     mt r;
     mt_seed(&r, oc_rd_seed(c->cfg.rd_seed, t, i + 1));
@@ -1172,7 +1207,9 @@ static void op_node(op_ctx *c, int i, pcand *m) {
       for (int q = 0; q < ng; q++) dup |= g[q] == m[ix].id - 1;
       if (!dup) g[ng++] = m[ix].id - 1;
     }
+    pf[OP_PROF_DRAWS] = r.used;
   }
+  pf[OP_PROF_TARGETS] = ng;
   c->ntgt_next[i] = ng;
   for (int q = 0; q < ng; q++) c->tgt_next[(size_t)i * FANOUT + q] = g[q];
   snap *sn = &c->snaps_next[i];
@@ -1187,6 +1224,7 @@ int op_tick(op_ctx *c) {
   c->nev = 0;
   memset(c->mc_sent, 0, sizeof(int32_t) * (size_t)n);
   memset(c->mc_recv, 0, sizeof(int32_t) * (size_t)n);
+  memset(c->prof, 0xFF, sizeof(int32_t) * (size_t)n * OP_PROF_WORDS); /* -1: the node did not run */
   /* counting sort of last tick's (sender, target) pairs by target, senders ascending */
   memset(c->rcv_off, 0, sizeof(int32_t) * (size_t)(n + 1));
   for (int s = 0; s < n; s++)
@@ -1209,7 +1247,7 @@ int op_tick(op_ctx *c) {
     op_node(c, i, m);
   }
   free(m);
-  qsort(c->ev, (size_t)c->nev, sizeof(oc_event), ev_canon);
+  if (c->nev) qsort(c->ev, (size_t)c->nev, sizeof(oc_event), ev_canon);
   snap *ts = c->snaps; c->snaps = c->snaps_next; c->snaps_next = ts;
   int32_t *tt = c->tgt; c->tgt = c->tgt_next; c->tgt_next = tt;
   tt = c->ntgt; c->ntgt = c->ntgt_next; c->ntgt_next = tt;
@@ -1244,6 +1282,103 @@ const char *op_dump(op_ctx *c, size_t *len) {
   }
   *len = c->dump.n;
   return c->dump.p ? c->dump.p : "";
+}
+
+/* the gossip targets every node drew in the last tick, in draw order ([n][5] node indices, counts [n]):
+ * the sends the next tick delivers */
+void op_targets(const op_ctx *c, int32_t *tgt, int32_t *ntgt) {
+  for (int i = 0; i < c->n; i++) {
+    ntgt[i] = c->ntgt[i];
+    for (int k = 0; k < FANOUT; k++) tgt[(size_t)i * FANOUT + k] = k < c->ntgt[i] ? c->tgt[(size_t)i * FANOUT + k] : 0;
+  }
+}
+
+void op_nodes(const op_ctx *c, int32_t *heartbeat, int32_t *failed) {
+  for (int i = 0; i < c->n; i++) {
+    heartbeat[i] = c->nd[i].hbctr;
+    failed[i] = c->nd[i].failed;
+  }
+}
+
+void op_last_profile(const op_ctx *c, int32_t *out) {
+  memcpy(out, c->prof, sizeof(int32_t) * (size_t)c->n * OP_PROF_WORDS);
+}
+
+/* Replace the whole state between ticks t - 1 and t: every node's view (id << 32 | hb, ids ascending,
+ * 0 = empty, [n][V]), heartbeat counters, crash flags and the targets drawn in t - 1. A state is
+ * checked as a whole before anything is written: the return value ORs an OP_LD_* bit per kind of
+ * violation found (0: loaded). The sent lists of t - 1 follow from the views: a sender's entries
+ * fresh at t - 1 (op_node's snapshot). */
+#define OP_INBOX_LISTS 63  /* lists one receiver takes per tick */
+#define OP_VIEW_AGES 32    /* a live node's entries are younger than this at t - 1 */
+int op_load_state(op_ctx *c, int t, const uint64_t *views, const int32_t *heartbeat, const int32_t *failed,
+                  const int32_t *targets, const int32_t *counts) {
+  if (!c || !views || !heartbeat || !failed || !targets || !counts) return OP_LD_EARG;
+  if (t < 5 + 1 || t > 16384 || c->V > 32) return OP_LD_EARG;
+  const int n = c->n, V = c->V, top = 2 * (t - 1);
+  int bad = 0;
+  int32_t *depth = (int32_t *)calloc((size_t)n, sizeof(int32_t));
+  for (int i = 0; i < n; i++) {
+    const uint64_t *vw = views + (size_t)i * V;
+    const int32_t hbc = heartbeat[i], f = failed[i], k = counts[i];
+    const int ran = hbc == top;
+    int self = 0, gap = 0;
+    for (int e = 0; e < V; e++) {
+      if (!vw[e]) { gap = 1; continue; }
+      const uint32_t id = (uint32_t)(vw[e] >> 32), hb = (uint32_t)vw[e];
+      if (gap) bad |= OP_LD_EGAP;
+      if (id < 1u || id > (uint32_t)n) bad |= OP_LD_EID;
+      if (e > 0 && (uint32_t)(vw[e - 1] >> 32) >= id) bad |= OP_LD_EORDER;
+      if (!(hb & 1u)) bad |= OP_LD_EHBPAR;
+      if (hb > (uint32_t)(2 * t - 3)) bad |= OP_LD_EHBTOP;
+      else if (f == 0 && (t - 1) - (int)((hb + 1u) >> 1) >= OP_VIEW_AGES) bad |= OP_LD_EAGE;
+      if (id == (uint32_t)(i + 1) && hb == (uint32_t)(hbc - 1)) self = 1;
+    }
+    if (!self) bad |= OP_LD_ESELF;
+    if (f != 0 && f != 1) bad |= OP_LD_EFAILED;
+    if (k < 0 || k > FANOUT) bad |= OP_LD_ECOUNT;
+    if (f == 0) {
+      if (!ran) bad |= OP_LD_EHEARTBEAT;
+    } else {
+      if ((hbc & 1) || hbc > top || hbc < 2) bad |= OP_LD_EHEARTBEAT;
+      if (k > 0 && !ran) bad |= OP_LD_ECRASHED; /* a node that did not run tick t - 1 sent nothing */
+    }
+    for (int q = 0; q < k && q < FANOUT; q++) {
+      const int32_t d = targets[(size_t)i * FANOUT + q];
+      int ok = d >= 0 && d < n && d != i, inview = 0;
+      for (int j = 0; j < q; j++) ok = ok && targets[(size_t)i * FANOUT + j] != d;
+      for (int e = 0; e < V && ok; e++) inview |= vw[e] != 0 && (uint32_t)(vw[e] >> 32) == (uint32_t)d + 1u;
+      if (!ok || !inview) bad |= OP_LD_ETARGET;
+      else if (++depth[d] > OP_INBOX_LISTS) bad |= OP_LD_EINBOX;
+    }
+  }
+  free(depth);
+  if (bad) return bad;
+  for (int i = 0; i < n; i++) {
+    pnode *p = &c->nd[i];
+    const uint64_t *vw = views + (size_t)i * V;
+    snap *sn = &c->snaps[i];
+    p->cnt = sn->n = 0;
+    for (int e = 0; e < V && vw[e]; e++) {
+      const int32_t id = (int32_t)(vw[e] >> 32), hb = (int32_t)(uint32_t)vw[e];
+      p->ids[p->cnt] = id;
+      p->hbs[p->cnt] = hb;
+      p->cnt++;
+      if (counts[i] > 0 && (t - 1) - (hb + 1) / 2 < TFAIL) { sn->ids[sn->n] = id; sn->hbs[sn->n] = hb; sn->n++; }
+    }
+    p->hbctr = heartbeat[i];
+    p->failed = failed[i];
+    c->ntgt[i] = counts[i];
+    for (int q = 0; q < FANOUT; q++) c->tgt[(size_t)i * FANOUT + q] = q < counts[i] ? targets[(size_t)i * FANOUT + q] : 0;
+    c->ntgt_next[i] = 0;
+    c->snaps_next[i].n = 0;
+  }
+  c->t = t;
+  c->nev = 0;
+  memset(c->mc_sent, 0, sizeof(int32_t) * (size_t)n);
+  memset(c->mc_recv, 0, sizeof(int32_t) * (size_t)n);
+  memset(c->prof, 0xFF, sizeof(int32_t) * (size_t)n * OP_PROF_WORDS);
+  return 0;
 }
 
 /* test telemetry: [0] = updateMyPos quirk firings so far, [1] = largest start-tick gap

@@ -115,6 +115,55 @@ const char *op_dump(op_ctx *c, size_t *len);
 /* per-node entries sent (before loss) / received (after loss) in the last tick */
 void op_last_msgcount(const op_ctx *c, int32_t *sent, int32_t *recv);
 uint64_t op_evict_key(uint64_t view_seed, int32_t t, int32_t obs, int32_t id);
+/* the last tick's gossip targets in draw order [n][5] (node indices) and their counts [n] */
+void op_targets(const op_ctx *c, int32_t *tgt, int32_t *ntgt);
+/* heartbeat counters and crash flags [n] */
+void op_nodes(const op_ctx *c, int32_t *heartbeat, int32_t *failed);
+/* Load the state between ticks t - 1 and t, with the arguments of the HIP path's gm_load_views /
+ * gm_load_views_commit for the whole cluster: views uint64 [n][V] (id << 32 | hb, ids ascending, 0 =
+ * empty), heartbeat / failed / counts [n], targets [n][5]; tick t runs next, and the config's
+ * crash_tick still applies. Returns 0, or -- nothing loaded -- the OR of an OP_LD_* bit per kind of
+ * violation: whatever the HIP path's load contract rejects (the same bits as its GM_PL_* codes). */
+enum {
+  OP_LD_EID = 0x1,          /* an id outside [1, n] */
+  OP_LD_EORDER = 0x2,       /* ids not strictly ascending */
+  OP_LD_EGAP = 0x4,         /* an entry after an empty slot */
+  OP_LD_EHBPAR = 0x8,       /* an even heartbeat */
+  OP_LD_EHBTOP = 0x10,      /* a heartbeat above 2(t - 1) - 1 */
+  OP_LD_EAGE = 0x20,        /* a live node's entry aged 32 or more at t - 1 */
+  OP_LD_ESELF = 0x40,       /* the node's own entry missing, or not {heartbeat - 1} */
+  OP_LD_EHEARTBEAT = 0x80,  /* live: heartbeat != 2(t - 1); crashed: odd, below 2 or above it */
+  OP_LD_EFAILED = 0x100,    /* a crash flag that is not 0 / 1 */
+  OP_LD_ECOUNT = 0x200,     /* a count outside 0..5 */
+  OP_LD_ETARGET = 0x400,    /* a target outside [0, n), the node itself, named twice, or not in its view */
+  OP_LD_ECRASHED = 0x800,   /* a crashed node with targets that did not run tick t - 1 */
+  OP_LD_EINBOX = 0x10000,   /* more than 63 lists for one receiver */
+  OP_LD_EARG = 0x20000      /* a null argument, t outside [6, 16384], or V above 32 */
+};
+int op_load_state(op_ctx *c, int t, const uint64_t *views, const int32_t *heartbeat, const int32_t *failed,
+                  const int32_t *targets, const int32_t *counts);
+/* Test telemetry of the last tick, int32 [n][OP_PROF_WORDS], -1 throughout for a node that did not run
+ * (crashed). It records which case of the tick each node was and never feeds a result. */
+enum {
+  OP_PROF_LISTS = 0,         /* lists delivered */
+  OP_PROF_UNION,             /* distinct ids after the merge */
+  OP_PROF_REMOVED,           /* entries the sweep removed (age >= TREMOVE) */
+  OP_PROF_REMOVE_EVENTS,     /* REMOVE events emitted (removed entries of the node's own list) */
+  OP_PROF_SWEPT,             /* size after the sweep */
+  OP_PROF_EVICTED,           /* 1 if the eviction ran (size after the sweep > V) */
+  OP_PROF_CLASS_SIZE,        /* eviction: candidates (self excluded) with the heartbeat of the last entry kept */
+  OP_PROF_CLASS_TAKEN,       /*   ... and how many of them were kept */
+  OP_PROF_GROUP_SIZE,        /* eviction: those of that class in the key group (key >> 26) of the last entry kept */
+  OP_PROF_GROUP_TAKEN,       /*   ... and how many of them were kept */
+  OP_PROF_CLASS_ORDINAL,     /* eviction: populated heartbeat classes fresher than that class */
+  OP_PROF_NUMPOT,            /* numpot of the gossip draw (may be <= 0) */
+  OP_PROF_TARGETS,           /* targets chosen */
+  OP_PROF_DRAWS,             /* S2 outputs the draw consumed */
+  OP_PROF_STALE,             /* entries of the final list aged TFAIL or more */
+  OP_PROF_SIZE,              /* size of the final list */
+  OP_PROF_WORDS
+};
+void op_last_profile(const op_ctx *c, int32_t *out);
 
 /* CPU-baseline sample: time node-ticks of the SCALED workload at size n (see ref_cpu.c) */
 int oc_bench_sample(int n, int lists, int max_nodes, double min_seconds, int *out_nodes, double *out_seconds);

@@ -86,6 +86,13 @@ def lib():
         L.op_events.restype = ctypes.c_size_t
         L.op_evict_key.argtypes = [ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
         L.op_evict_key.restype = ctypes.c_uint64
+        L.op_targets.argtypes = [ctypes.c_void_p, P(ctypes.c_int32), P(ctypes.c_int32)]
+        L.op_targets.restype = None
+        L.op_nodes.argtypes = [ctypes.c_void_p, P(ctypes.c_int32), P(ctypes.c_int32)]
+        L.op_nodes.restype = None
+        L.op_last_profile.argtypes = [ctypes.c_void_p, P(ctypes.c_int32)]
+        L.op_last_profile.restype = None
+        L.op_load_state.argtypes = [ctypes.c_void_p, ctypes.c_int, P(ctypes.c_uint64)] + [P(ctypes.c_int32)] * 4
         _lib = L
     return _lib
 
@@ -200,6 +207,23 @@ class Oracle:
         return sent, recv
 
 
+# op_load_state's violation bits (ref_cpu.h OP_LD_*) and op_last_profile's columns (OP_PROF_*)
+OP_LD = {"EID": 0x1, "EORDER": 0x2, "EGAP": 0x4, "EHBPAR": 0x8, "EHBTOP": 0x10, "EAGE": 0x20, "ESELF": 0x40,
+         "EHEARTBEAT": 0x80, "EFAILED": 0x100, "ECOUNT": 0x200, "ETARGET": 0x400, "ECRASHED": 0x800,
+         "EINBOX": 0x10000, "EARG": 0x20000}
+PROFILE_COLUMNS = ("lists", "union", "removed", "remove_events", "swept", "evicted", "class_size", "class_taken",
+                   "group_size", "group_taken", "class_ordinal", "numpot", "targets", "draws", "stale", "size")
+
+
+class OracleLoadError(ValueError):
+    """op_load_state refused a state; bits = the OR of the OP_LD violations found"""
+
+    def __init__(self, bits):
+        self.bits = bits
+        names = [k for k, b in OP_LD.items() if bits & b]
+        super().__init__(f"op_load_state: 0x{bits:x} ({' | '.join(names)})")
+
+
 class PartialOracle:
     """PARTIAL mode (V-entry views, scenario S-C): the oracle IS the specification."""
 
@@ -212,6 +236,7 @@ class PartialOracle:
         if not self.h:
             raise ValueError("op_create failed")
         self.n = n
+        self.v = v
 
     def close(self):
         if self.h:
@@ -244,6 +269,65 @@ class PartialOracle:
         recv = np.zeros(self.n, dtype=np.int32)
         self.L.op_last_msgcount(self.h, _i32p(sent), _i32p(recv))
         return sent, recv
+
+    def load_state(self, t, views, heartbeat, failed, targets, counts):
+        """Replace the state between ticks (op_load_state); tick t runs next. The arguments of
+        Simulator.load_views for the whole cluster: views uint64 [n][V] (id << 32 | hb), heartbeat /
+        failed / counts [n], targets [n][5]. Raises OracleLoadError for a state the HIP path's load
+        contract rejects; nothing is loaded then."""
+        vw = np.ascontiguousarray(views, dtype=np.uint64)
+        if vw.shape != (self.n, self.v):
+            raise ValueError(f"load_state: views of shape {vw.shape}, the oracle holds [{self.n}][{self.v}]")
+        arrs = [np.ascontiguousarray(a, dtype=np.int32).reshape(shape) for a, shape in
+                ((heartbeat, self.n), (failed, self.n), (targets, (self.n, 5)), (counts, self.n))]
+        rc = self.L.op_load_state(self.h, int(t), vw.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                  *[_i32p(a) for a in arrs])
+        if rc:
+            raise OracleLoadError(rc)
+
+    def load_snapshot(self, snap):
+        """load_state from a cluster view snapshot (membership.state.VIEW_KEYS form, n0 = 0)"""
+        if snap["n0"] != 0:
+            raise ValueError("load_snapshot: a cluster snapshot starts at node 0")
+        self.load_state(snap["t"], snap["views"], snap["heartbeat"], snap["failed"], snap["targets"], snap["counts"])
+
+    def targets(self):
+        """(targets int32 [n][5] in draw order, counts [n]) of the last tick, as read_targets returns them"""
+        tg = np.zeros((self.n, 5), dtype=np.int32)
+        cnt = np.zeros(self.n, dtype=np.int32)
+        self.L.op_targets(self.h, _i32p(tg), _i32p(cnt))
+        return tg, cnt
+
+    def nodes(self):
+        """[n][4] inited / inGroup / failed / heartbeat, as read_nodes returns them"""
+        hb = np.zeros(self.n, dtype=np.int32)
+        failed = np.zeros(self.n, dtype=np.int32)
+        self.L.op_nodes(self.h, _i32p(hb), _i32p(failed))
+        one = np.ones(self.n, dtype=np.int32)
+        return np.stack([one, one, failed, hb], axis=1)
+
+    def views(self):
+        """uint64 [n][V] (id << 32 | hb, 0 = empty), parsed from the dump: what read_views returns"""
+        out = np.zeros((self.n, self.v), dtype=np.uint64)
+        for i, line in enumerate(self.dump().splitlines()):
+            for k, ent in enumerate(line.split()[7:]):
+                ident, hb, _ = ent.split(b":")
+                out[i, k] = (int(ident) << 32) | int(hb)
+        return out
+
+    def snapshot(self):
+        """the state between ticks as a cluster view snapshot (membership.state.VIEW_KEYS form)"""
+        st = self.nodes()
+        tg, cnt = self.targets()
+        return {"t": self.time, "n0": 0, "views": self.views(), "heartbeat": st[:, 3].copy(),
+                "failed": st[:, 2].copy(), "targets": tg, "counts": cnt}
+
+    def profile(self):
+        """{column: int32 [n]} of the last tick's telemetry (op_last_profile, PROFILE_COLUMNS); -1 for a
+        node that did not run"""
+        out = np.zeros((self.n, len(PROFILE_COLUMNS)), dtype=np.int32)
+        self.L.op_last_profile(self.h, _i32p(out))
+        return {k: out[:, j].copy() for j, k in enumerate(PROFILE_COLUMNS)}
 
 
 def crash_set(n, count, seed):

@@ -1,8 +1,9 @@
 """PARTIAL: a view state loaded into a context (gm_load_views_begin / gm_load_views / gm_load_views_commit,
 membership.state.view_snapshot / view_restore) continues exactly as the run it was taken from.
 
-The oracle has no PARTIAL load, so a continued run is compared with the oracle's own uninterrupted
-run, and layouts (one context, G loopback row shards, one forced RCCL rank) with each other."""
+A continued run is compared with the oracle's own uninterrupted run, and layouts (one context, G loopback
+row shards, one forced RCCL rank) with each other; the chosen state of section 5 is loaded into the oracle
+as well (PartialOracle.load_snapshot). States built on the node tick's edges: test_gpu_partial_edges.py."""
 import copy
 import ctypes
 
@@ -227,25 +228,34 @@ def chosen_state(n, v, t, depth):
 def test_chosen_state_reaches_all_three_node_kernels():
     """Inbox depths 0..20 on 21 receivers spread over the shards: past P_KSMALL = 12 (gm_p_tick_big) and
     P_KP = 16 (gm_p_tick_huge). tick_stats exposes the first tick's "lists merged" as their sum and
-    their maximum, not per node: 210 lists in all, 20 at most, on one context and summed over G = 3."""
+    their maximum, not per node: 210 lists in all, 20 at most, on one context and summed over G = 3.
+    The oracle takes the same state: both layouts equal it, not only each other."""
     n, v, t = 300, 32, 15
     snap = chosen_state(n, v, t, {14 * d: d for d in range(21)})
     assert snap["counts"].sum() == 210
     one, three = make(n, v, drop=0), make(n, v, 3, drop=0)
+    ora = oracle_py.PartialOracle(n, v=v, **KW)
+    ora.load_snapshot(snap)
     restore(one, snap)
     restore(three, snap)
-    assert dump(three) == dump(one)
+    assert dump(three) == dump(one) == ora.dump()
     for k in range(5):
         tick(one)
         tick(three)
+        ora.tick()
         if k == 0:
             st = [s.tick_stats() for s in one + three]
             assert st[0]["lists"] == 210 and st[0]["max_inbox"] == 20
             assert sum(x["lists"] for x in st[1:]) == 210 and max(x["max_inbox"] for x in st[1:]) == 20
             sizes = one[0].view_census(records=False)[2]
             assert sizes.sum() == n and sizes[v] == n  # every view was full and stays full
-        assert events(three) == events(one), f"events differ at tick {t + k}"
+        ev = events(one)
+        assert events(three) == ev, f"events differ at tick {t + k}"
         assert dump(three) == dump(one), f"views differ at tick {t + k}"
+        assert ev == sorted(ora.events()), f"events differ from the oracle's at tick {t + k}"
+        assert dump(one) == ora.dump(), f"views differ from the oracle's at tick {t + k}"
+        if k == 0:
+            assert ora.profile()["lists"][[14 * d for d in range(21)]].tolist() == list(range(21))
     assert all(s.tick_stats()["err"] == 0 for s in one + three)
 
 
