@@ -8,10 +8,6 @@
 // ------------------------------------------------------------ gm_s_band fast path
 // Lane-mask bit p in esc_mask16's order is cell esc_cell(p); esc_bit is the inverse.
 __device__ __forceinline__ int esc_bit(int q) { return ((q & 3) << 3) | (q >> 2); }
-// set bits of a wave mask below this lane
-__device__ __forceinline__ int p_lanes_below(uint64_t b) {
-  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-}
 // One marked cell of the fast path, exactly (16-bit cell c: the merged byte y widened, or the escaped
 // cell re-based and merged; the general path's arithmetic): its stored byte, payload nibble (high-
 // nibble form), whether it is removed (TREMOVE) or needs the wide payload plane (bail), and the
@@ -375,7 +371,7 @@ __device__ __forceinline__ bool unit_fast(const SState &s, int t, const UnitIn<B
     if (eb_out != 0) {
       const EscList l = esc_list(s, par, slab, r, eb_out);
       if (sv) {
-        *l.at(p_lanes_below(svb)) = sent;
+        *l.at(lanes_below(svb)) = sent;
         if ((sent >> 16) < (uint32_t)S_CELL(s.lag_hmin, 0)) atomicOr(s.err, GM_ERR_LAG);
       }
       if (emany) esc_emit(lds, lane, l, ns + eoff, em, li * Q, etot <= S_ESC_IN, s.err, s.lag_hmin);

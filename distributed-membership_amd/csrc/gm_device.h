@@ -156,6 +156,28 @@ __device__ __forceinline__ void gm_mt_first16(uint32_t seed, uint32_t out[16]) {
   }
 }
 
+// set bits of a wave mask (a ballot) in the lanes below this one
+__device__ __forceinline__ int lanes_below(uint64_t b) {
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+}
+
+// inclusive scan within each 16-lane DPP row: row_shr 1/2/4/8 (lanes a DPP source does not reach add 0)
+__device__ __forceinline__ int row16_scan(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);  // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);  // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);  // row_shr:4
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);  // row_shr:8
+  return v;
+}
+// wave-wide inclusive scan on DPP: the rows' scans, then row_bcast15 / row_bcast31 carry the row
+// totals upward
+__device__ __forceinline__ int dpp_scan(int v) {
+  v = row16_scan(v);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
+  return v;
+}
+
 // Index of the ix-th set bit (0-based) of a bitmap `bits` with exclusive
 // per-word prefix popcounts `pre` (nw words). Caller guarantees ix < total.
 __device__ __forceinline__ int gm_rank_select(const uint64_t *bits, const uint32_t *pre, int nw, uint32_t ix) {

@@ -71,20 +71,6 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-__device__ __forceinline__ int mbcnt(uint64_t m) {  // set bits of m in the lanes below
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-}
-
-__device__ __forceinline__ int wave_incl_scan(int v) {  // DPP: rows by row_shr, then row_bcast
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);
-  return v;
-}
-
 // Every kernel of the tick exists twice over ONE body (gm_faithful_tick.h, included as text): gm_f_*
 // runs it for the cluster given as kernel arguments (gm_tick), gm_fb_* for the member blockIdx.y of a
 // batch (gm_batch_tick), whose state and tick it loads from the batch's slots first.

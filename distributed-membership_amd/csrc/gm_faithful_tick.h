@@ -49,7 +49,7 @@
     // counts of segments 2l, 2l+1 and the number of matches in the segments below 2l
     const uint32_t wd = lane < nsw ? cw[me * nsw + lane] : 0u;
     const int clo = (int)(wd & 0xFFFFu), chi = (int)(wd >> 16);
-    const int incl = wave_incl_scan(clo + chi);
+    const int incl = dpp_scan(clo + chi);
     const int k = __builtin_amdgcn_readlane(incl, 63);
     if (k == 0) continue;
     const int excl = incl - clo - chi;
@@ -75,7 +75,7 @@
           for (int q = 0; q < 4; q++) {
             h[q] = jb + q < s1 && (e[q] >> 16) == me;
             b[q] = __ballot(h[q]);
-            rk += mbcnt(b[q]);
+            rk += lanes_below(b[q]);
           }
 #pragma unroll
           for (int q = 0; q < 4; q++) {

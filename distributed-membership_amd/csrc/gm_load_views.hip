@@ -24,7 +24,7 @@
 //                stores hbctr, failed, targets and rowstat's count word, clears the node's event words
 //                and rowstat[.][0, 2] and both parities' inbox counters.
 //   gm_pl_inbox  thread per node: each LOCAL target's inbox of parity t & 1 gets the node's row by one
-//                returning atomic (p_node's send round: row[1 + slot] = li); a receiver past kcap is
+//                returning atomic (p_node's send round, p_send: row[1 + slot] = li); a receiver past kcap is
 //                GM_PL_EINBOX. Targets owned by another row shard are left to the exchange.
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-// gm_partial.h -- device state of the PARTIAL-view tick (see gm_partial.hip).
+// gm_partial.h -- device state of the PARTIAL-view tick (see gm_partial.hip for the files of the group).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,8 +22,7 @@
 #ifndef P_NPW_CHUNK
 #define P_NPW_CHUNK 4    // the same for a row shard's chunk launches (fewer nodes per launch: a finer last round)
 #endif
-#define P_EV_ADD 1u
-#define P_EV_REMOVE 2u
+#define P_EV_REMOVE 2u  // kind of an ev record (the only one: joins are a mask, ev_jm)
 // Wire entry of an exchanged list: id | (2t-1 - hb) << 25, only entries fresh at the
 // sender's tick t (the receiver drops the others anyway), 0 = none: 4 bytes instead of 8.
 #define P_WIRE_IDBITS 25
@@ -100,7 +99,8 @@ struct PState {
 #define GM_PL_EINVAL_MASK 0xFFFFu
 #define GM_PL_EINBOX 0x10000u  // more lists for one receiver than its inbox holds
 
-// host launch wrappers (gm_partial.hip, gm_view_census.hip, gm_view_detect.hip, gm_load_views.hip)
+// host launch wrappers (gm_partial.hip; unpack and pack: gm_partial_xchg.hip; gm_view_census.hip,
+// gm_view_detect.hip, gm_load_views.hip)
 hipError_t gm_launch_partial_init(const PState &s, int t0, uint64_t init_seed, hipStream_t st);
 hipError_t gm_launch_partial_unpack(const PState &s, int t, int base, int nrecv, hipStream_t st);
 hipError_t gm_launch_partial_pack(const PState &s, int t, int c, hipStream_t st);

@@ -268,22 +268,7 @@ __device__ __forceinline__ u16x2 widen2(u16x2 x, u16x2 nz) {
   return nz * (u16x2)(7168) + ((x & (u16x2)(0xF0)) * (u16x2)(3) + x);
 }
 
-// inclusive scan within each 16-lane DPP row: row_shr 1/2/4/8 (lanes a DPP source does not reach add 0)
-__device__ __forceinline__ int row16_scan(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);  // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);  // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);  // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);  // row_shr:8
-  return v;
-}
-// wave-wide inclusive scan on DPP: the rows' scans, then row_bcast15 / row_bcast31 carry the row
-// totals upward
-__device__ __forceinline__ int dpp_scan(int v) {
-  v = row16_scan(v);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
-  return v;
-}
+// (row16_scan and dpp_scan, the DPP scans of a 16-lane row and of the wave, are gm_device.h's)
 
 // Stored bytes of two swept cells (pres = min(v2, 1)): tt = v2 - (S_CELL(230, 0) - 1) (wraps below
 // h = 230) = (h - 230) << 5 | (age + 1); representable iff nothing above the h field (h <= 254, no

@@ -160,7 +160,7 @@ __device__ __forceinline__ uint32_t gm_mt_batch(GmLazyMT &mt, uint32_t *mts, uin
   return raw;
 }
 
-// 16 lanes per row (gm_s_pick0, gm_s_draw0): row16_scan is gm_scaled.h's, with dpp_scan
+// 16 lanes per row (gm_s_pick0, gm_s_draw0): row16_scan is gm_device.h's, with dpp_scan
 __device__ __forceinline__ int row16_bcast(int v, int g, int q) { return __shfl(v, 16 * g + q, 64); }
 __device__ __forceinline__ uint32_t row16_bits(uint64_t bal, int g) { return (uint32_t)(bal >> (16 * g)) & 0xFFFFu; }
 

@@ -6,7 +6,7 @@
 // 24 n bytes plus the two histograms go back (gm_host_read.hip gm_view_census). Nothing the tick kernels
 // read is written: the reducer's only outputs are its own scratch.
 //
-// An entry's timestamp is derived from its heartbeat (ts = (hb + 1) / 2, gm_partial.hip), so its age
+// An entry's timestamp is derived from its heartbeat (ts = (hb + 1) / 2, gm_partial_node.h), so its age
 // and its heartbeat lag are one number: lag = (2T - 1 - hb) / 2. Everything is accumulated in lag
 // units and converted once per subject at the flush.
 //

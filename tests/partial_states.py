@@ -1,4 +1,4 @@
-"""PARTIAL states built to sit on the edges of the node tick (gm_partial.hip p_node): plain NumPy plus the
+"""PARTIAL states built to sit on the edges of the node tick (gm_partial_node.h p_node): plain NumPy plus the
 oracle's op_evict_key, no GPU code. Every builder returns a cluster view snapshot (membership.state
 VIEW_KEYS form: t, n0 = 0, views, heartbeat, failed, targets, counts) that satisfies the load contract --
 own entry 2(t - 1) - 1, every target in the sender's view, ids ascending, ages below GM_VIEW_AGES -- plus

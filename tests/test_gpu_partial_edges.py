@@ -1,4 +1,4 @@
-"""PARTIAL: the node tick (gm_partial.hip p_node, all three tables) against the oracle on states built to
+"""PARTIAL: the node tick (gm_partial_node.h p_node, all three tables) against the oracle on states built to
 sit on its edges (tests/partial_states.py), loaded into both sides: the oracle by op_load_state, the
 contexts by gm_load_views. What each builder reaches is asserted on the CPU, by the oracle's telemetry
 alone (test_oracle_partial_load.py, the coverage conditions):
