@@ -13,13 +13,13 @@ LIB := $(PKG)/lib/libgm.so
 KOBJS := $(PKG)/build/gm_faithful.o $(PKG)/build/gm_scaled.o $(PKG)/build/gm_band.o $(PKG)/build/gm_draw.o \
          $(PKG)/build/gm_partial.o $(PKG)/build/gm_partial_xchg.o $(PKG)/build/gm_detect.o \
          $(PKG)/build/gm_load.o $(PKG)/build/gm_census.o $(PKG)/build/gm_view_census.o $(PKG)/build/gm_read.o \
-         $(PKG)/build/gm_load_views.o $(PKG)/build/gm_view_detect.o \
+         $(PKG)/build/gm_load_views.o $(PKG)/build/gm_view_detect.o $(PKG)/build/gm_digest.o \
          $(PKG)/build/gm_host.o $(PKG)/build/gm_host_faithful.o $(PKG)/build/gm_host_batch.o $(PKG)/build/gm_host_scaled.o \
          $(PKG)/build/gm_host_shard.o $(PKG)/build/gm_host_partial.o $(PKG)/build/gm_host_events.o \
          $(PKG)/build/gm_host_read.o $(PKG)/build/gm_host_stage.o $(PKG)/build/gm_host_load.o \
-         $(PKG)/build/gm_host_view_detect.o
+         $(PKG)/build/gm_host_view_detect.o $(PKG)/build/gm_host_digest.o
 HDRS := include/gm_abi.h $(CSRC)/gm_device.h $(CSRC)/gm_faithful.h $(CSRC)/gm_scaled.h $(CSRC)/gm_partial.h \
-        $(CSRC)/gm_partial_node.h $(CSRC)/gm_host.h $(CSRC)/gm_band.h $(CSRC)/gm_select.h
+        $(CSRC)/gm_partial_node.h $(CSRC)/gm_host.h $(CSRC)/gm_band.h $(CSRC)/gm_select.h $(CSRC)/gm_digest.h
 # kernel files compiled as part of another unit (gm_band.hip, gm_draw.hip include them)
 HDRS += $(CSRC)/gm_band_fast.hip $(CSRC)/gm_pick.hip
 # the FAITHFUL kernel bodies, included as text by gm_faithful.hip

@@ -10,6 +10,7 @@
 //   gm_host_events.hip    event drains, detection recorder, msgcount
 //   gm_host_view_detect.hip  PARTIAL detection recorder (gm_view_detect_*)
 //   gm_host_read.hip      read-backs: rows, tables, views, nodes, targets, the censuses
+//   gm_host_digest.hip    state digests: gm_digest, the per-tick recorder (gm_digest_record / _trace)
 //   gm_host_stage.hip     the staged block of gm_read_rows and the loads: size, timing, stats
 //   gm_host_load.hip      gm_load_*, gm_load_views_*: one block loop, one commit tail
 #pragma once
@@ -71,6 +72,18 @@ struct gm_view_detect_state {
   uint64_t *tl = nullptr;             // [tmax][GM_VIEW_DETECT_COLS]
   uint32_t *cls = nullptr;            // the crash bitmap of the cluster as the next tick will see it (bit id - 1)
   uint32_t *status = nullptr;         // the reducer's status word (GM_VD_E*)
+};
+
+// State digests (gm_digest, gm_digest_record): device scratch, allocated by the first call of either.
+// blob: the word arrays rows, nodes [n] (PARTIAL: [nloc]), the two sums, the status word of gm_digest.
+// The recorder (tmax 0 = off) keeps the trace and a status word of its own, and uses the word arrays as
+// each recorded tick's scratch (stream-ordered with gm_digest's use of them).
+struct gm_digest_state {
+  uint8_t *blob = nullptr;
+  int32_t *fail_t = nullptr;         // join ramp: device copy of gm_ctx.fail_t (gm_read_nodes' inGroup rule)
+  int tmax = 0;
+  uint64_t *trace = nullptr;         // [tmax][2]
+  uint32_t *status = nullptr;        // the recorded ticks' status word
 };
 
 #define GM_STAGE_BYTES (256ull << 20)  // what a staged call's rows of one launch may take on the device
@@ -202,6 +215,7 @@ struct gm_ctx {
   gm_view_detect_state vdet;
   gm_load_stage vl;
   gm_shard_exchange xch;  // SCALED column shards, PARTIAL row shards
+  gm_digest_state dg;     // SCALED, PARTIAL
 };
 
 namespace gmh {
@@ -339,6 +353,10 @@ int before_tick_events(gm_ctx *c);
 // gm_host_view_detect.hip
 int view_detect_flags(gm_ctx *c);
 int view_detect_tick(gm_ctx *c, int t, hipStream_t st);
+
+// gm_host_digest.hip
+int digest_flags(gm_ctx *c);
+int digest_tick(gm_ctx *c, int t, hipStream_t st);
 
 // gm_host_stage.hip
 int stage_cap(size_t budget, size_t row_bytes, size_t rows, const char *env);

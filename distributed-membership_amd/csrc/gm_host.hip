@@ -268,6 +268,7 @@ extern "C" int gm_set_failed(gm_ctx *c, const int32_t *idx, int32_t n) {
                      hipMemcpyHostToDevice));
   if (part && c->ph.sharded) TRY(partial_caps(c));  // the exchange blocks follow the live nodes per shard
   if (part) TRY(view_detect_flags(c));  // while recording: the crash bitmap the next tick's reducer reads
+  TRY(digest_flags(c));  // join ramp, once a digest was taken: the crashed nodes' last ticks on the device
   return GM_OK;
 }
 

@@ -306,6 +306,7 @@ int gmh::tick_partial(gm_ctx **g, int G) {
   if (!L->ph.sharded) {
     HIPCHECK(gm_launch_partial_chunk(L->p, t, mt(L, par), 0, st));
     TRY(view_detect_tick(L, t, st));  // while recording: the tick's final views and records, reduced
+    TRY(digest_tick(L, t, st));       // while recording: the state the tick leaves, digested
     if (k1) HIPCHECK(hipEventRecord(k1, st));
   } else {
     bool check = false;
@@ -336,6 +337,7 @@ int gmh::tick_partial(gm_ctx **g, int G) {
     // while recording: every member's reducer behind the last chunk's node kernels, on the compute
     // stream beside the exchange (which only reads what the reducer reads)
     for (int i = 0; i < G; i++) TRY(view_detect_tick(g[i], t, st));
+    for (int i = 0; i < G; i++) TRY(digest_tick(g[i], t, st));  // reads what the node kernels left, as the reducer
     if (k1) HIPCHECK(hipEventRecord(k1, st));
     for (int q = 0; q < K; q++) {
       HIPCHECK(hipStreamWaitEvent(L->xch.stream, L->xch.chunk_ev[q], 0));

@@ -293,6 +293,7 @@ int gmh::tick_scaled(gm_ctx *c) {
   if (c->timing) TRY(timing_slot(c, &k0, &k1, c->stream));
   HIPCHECK(gm_launch_tick(c->s, c->t, drop ? c->cfg.drop_pct : -1, c->stream, k0, k1, true));
   TRY(detect_tick(c, c->t, c->stream));
+  TRY(digest_tick(c, c->t, c->stream));  // while recording: the state the tick leaves, digested
   if (c->s.mc_sent && c->t < c->s.mc_tmax) {
     HIPCHECK(gm_launch_msgcount(c->s, c->t, drop, 0, c->stream));
     HIPCHECK(gm_launch_msgcount(c->s, c->t, drop, 1, c->stream));

@@ -128,6 +128,8 @@ SIGNATURES = {
     "gm_view_detect_record": [_ctx, _i32], "gm_view_detect": [_ctx, _P(GmViewDetectRec)],
     "gm_view_detect_timeline": [_ctx, _i32, _P(_u64)],
     "gm_read_rows": [_ctx, _i32, _i32, _P(_i32), _P(_i32)], "gm_read_rows_stats": [_ctx, _P(_f64)],
+    "gm_digest": [_ctx, _P(_u64), _P(_u64), _P(_u64)], "gm_digest_record": [_ctx, _i32],
+    "gm_digest_trace": [_ctx, _i32, _P(_u64)],
     "gm_load_views_begin": [_ctx, _i32], "gm_load_views": [_ctx, _i32, _i32, _P(_u64)],
     "gm_load_views_commit": _load4, "gm_load_views_stats": [_ctx, _P(_f64)],
     "gm_batch_create": [_P(_ctx), _i32, _P(_ctx)], "gm_batch_tick": [_ctx], "gm_batch_destroy": [_ctx],
@@ -384,6 +386,33 @@ class Simulator:
         recorded in each tick < t (a row shard: of its own observers)"""
         out = np.zeros((t, GM_VIEW_DETECT_COLS), dtype=np.uint64)
         self._call("gm_view_detect_timeline", self.h, t, _ptr(out, ctypes.c_uint64))
+        return out
+
+    def digest(self, rows=True, nodes=True):
+        """SCALED / PARTIAL: the layout-independent digest of the state as of the last tick, computed on
+        the device (gm_digest; membership.digest restates the definition in NumPy). Returns a dict of
+        table, nodes (ints: the two sums), rows, node_words (uint64 arrays, one word per observer row
+        and per node of this context -- n for SCALED, a row shard's own nodes for PARTIAL -- or None
+        where not asked for) and r0, the global index of the arrays' first node."""
+        part = self.mode == GM_MODE_PARTIAL
+        r0, count = self.shard_layout() if part else (0, self.n)
+        sums = np.zeros(2, dtype=np.uint64)
+        rw = np.zeros(count, dtype=np.uint64) if rows else None
+        nw = np.zeros(count, dtype=np.uint64) if nodes else None
+        self._call("gm_digest", self.h, _ptr(sums, ctypes.c_uint64), _ptr(rw, ctypes.c_uint64) if rows else None,
+                   _ptr(nw, ctypes.c_uint64) if nodes else None)
+        return {"table": int(sums[0]), "nodes": int(sums[1]), "rows": rw, "node_words": nw, "r0": r0}
+
+    def digest_record(self, tmax):
+        """SCALED (one context) / PARTIAL: record the digest's two sums after every tick < tmax, from the
+        next tick on, on the device (gm_digest_record)"""
+        self._call("gm_digest_record", self.h, tmax)
+
+    def digest_trace(self, t):
+        """uint64 [t, 2]: (table, nodes) as digest() would have returned them right after each tick < t;
+        a tick that was not recorded is (0, 0). A row shard records its own nodes: the shards' traces add up."""
+        out = np.zeros((t, 2), dtype=np.uint64)
+        self._call("gm_digest_trace", self.h, t, _ptr(out, ctypes.c_uint64))
         return out
 
     def read_row(self, r, c0=0, length=None):

@@ -24,6 +24,7 @@ import os
 
 import numpy as np
 
+from . import digest as _digest
 from .abi import default_chunk_rows
 
 KEYS = ("t", "hb", "ts", "heartbeat", "failed", "targets", "counts")
@@ -104,6 +105,17 @@ def restore(sim, snap, chunk_rows=None):
     """Load a snapshot into a SCALED context (created with init_mode 0 or 1); tick snap["t"] runs next."""
     sim.load_state(snap["t"], snap["hb"], snap["ts"], snap["heartbeat"], snap["failed"], snap["targets"],
                    snap["counts"], chunk_rows=chunk_rows)
+
+
+def verify(sim, snap):
+    """Does the SCALED context hold the snapshot's state? Compares sim.digest(), computed where the state
+    lives, with the snapshot's (membership.digest.of_snapshot, block by block over memory-mapped tables):
+    the check after a restore that reads no table back. snap is full-width or already cut to the
+    context's columns; returns the node indices whose row word or node word differ (empty: equal)."""
+    c0, w = sim.shard_layout()
+    if snap["hb"].shape[1] != w:
+        snap = slice_columns(snap, (c0, w))
+    return _digest.diff(sim.digest(), _digest.of_snapshot(snap, c0))
 
 
 def save(snap, path):
@@ -208,6 +220,15 @@ def view_restore(sim, snap, chunk_rows=None):
                          f"{tuple(sim.shard_layout())} of {sim.n}: cut it with slice_rows")
     sim.load_views(snap["t"], snap["views"], snap["heartbeat"], snap["failed"], snap["targets"], snap["counts"],
                    chunk_rows=chunk_rows)
+
+
+def view_verify(sim, snap):
+    """Does the PARTIAL context hold the view snapshot's state (cut to the context's own nodes where it
+    covers more)? Returns the global node indices whose row word or node word differ (empty: equal)."""
+    n0, nloc = sim.shard_layout()
+    if (int(snap["n0"]), snap["views"].shape[0]) != (n0, nloc):
+        snap = slice_rows(snap, n0, nloc)
+    return _digest.diff(sim.digest(), _digest.of_view_snapshot(snap))
 
 
 def slice_rows(snap, n0, nloc):

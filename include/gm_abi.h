@@ -28,6 +28,10 @@
  *                   lines: who was removed, by how many observers, when, and who by mistake
  *   gm_msgcount     EmulNet::sent_msgs / recv_msgs as dumped by ENcleanup (EmulNet.cpp:184-220)
  *   gm_dump_tables  Member::memberList of every node (Member.h:89-122), for parity tests
+ *   gm_digest, gm_digest_record, gm_digest_trace
+ *                   Member::memberList of every node (Member.h:89-122) with Member's flags and
+ *                   heartbeat and the gossipnodes of nodeLoopOps (MP1Node.cpp:449-489): the content
+ *                   gm_dump_tables renders, hashed where it lives
  *   gm_destroy      Application::~Application / ENcleanup storage release
  *   gm_batch_tick   R independent Application processes, each at its own globaltime, advanced by
  *                   one mp1Run each (the grader's three testcases, a seed ensemble)
@@ -436,6 +440,68 @@ int gm_view_detect(gm_ctx *ctx, gm_view_detect_rec *out);
  * before recording began is all zero. A row shard reports its own observers' rows; the shards'
  * timelines add up. GM_ESTATE as gm_view_detect. */
 int gm_view_detect_timeline(gm_ctx *ctx, int32_t t, uint64_t *out);
+
+/* ---- SCALED / PARTIAL: layout-independent digests of the state between two ticks, computed on the
+ * device (the tables and views are not copied to the host). The definition is normative; all
+ * arithmetic is mod 2^64, mix is splitmix64's finalizer (gm_mix64, csrc/gm_device.h):
+ *
+ *   GM_DIGEST_VERSION 1
+ *   KCOL  = 0x6D656D6265727368   KNODE = 0x6E6F646573746174   KROW = 0x726F77666F6C6421
+ *
+ *   kcol(c)         = mix(KCOL ^ c)                        c = global subject index (id - 1)
+ *   cell(c, hb, ts) = mix(kcol(c) ^ ((uint64)hb << 32 | (uint32)ts))
+ *   rows[r]         = sum of cell(c, hb, ts) over the PRESENT entries (hb >= 0) of observer r among this
+ *                     context's columns
+ *                     -- (hb, ts) exactly what gm_read_table / gm_read_rows return
+ *                     -- PARTIAL: the entries of the view gm_read_views returns, c = id - 1, ts = (hb + 1) / 2
+ *   knode(r)        = mix(KNODE ^ r)                       r = global node index
+ *   nodes[r]        = mix(knode(r) ^ ((uint64)heartbeat << 8 | count << 3 | failed << 2 | inGroup << 1 | inited))
+ *                     + sum over q < count of mix(mix(knode(r) + q + 1) ^ (uint64)target_q)
+ *                     -- the four words of gm_read_nodes, and counts / targets (draw order) of gm_read_targets
+ *                     -- slots >= count are not read: the device array holds anything there
+ *   fold(r, x)      = mix(mix(KROW ^ r) ^ x)
+ *   sums[0] = sum over r of fold(r, rows[r])   sums[1] = sum over r of fold(r, nodes[r])   over this context's nodes
+ *
+ * An absent entry adds nothing; a present {0, 0} (cold start) adds mix(kcol(c)), so it differs from an
+ * absent one. Rows of crashed observers (frozen tables, based at the tick they last ran) are part of the
+ * state and are digested -- here the digest differs from the censuses. The definition does not depend on
+ * the band width, on the fast or the general path, on column or row sharding, or on whether the state was
+ * ticked, loaded or produced by the oracle (membership.digest restates it in NumPy).
+ * SCALED column shard: rows[r] covers its own columns [c0, c0 + w); nodes[r] is the node word for
+ * c0 <= r < c0 + w and 0 elsewhere (a shard's heartbeat counter is current only for the nodes whose
+ * column it holds). The shards' rows and nodes therefore ADD UP element-wise to the single context's
+ * arrays; a shard's own sums are of its partial words and only comparable between equal layouts: the
+ * cluster's sums come from folding the added arrays (membership.digest.merge_columns).
+ * PARTIAL row shard: arrays of its own nloc nodes, with global r: the arrays concatenate and the
+ * shards' sums add up to the cluster's (membership.digest.merge_rows). */
+#define GM_DIGEST_VERSION 1
+/* SCALED / PARTIAL; FAITHFUL: GM_EUNSUPPORTED. The state as of the last tick run (after create or a
+ * load commit: as created / loaded). sums[2], rows and nodes [n] (PARTIAL: [nloc]); any of the three
+ * pointers may be NULL, not all (GM_EINVAL). Column shards, row shards, join-ramp contexts and contexts
+ * recording msgcount or detection are supported. The call is a read-back: it settles pending draw
+ * rounds, waits for the enqueued ticks (both streams of a row shard), reports a latched device error and
+ * writes nothing a tick or another read observes; its device scratch (one block: the two word arrays,
+ * the sums, the status word) is allocated by the first call and freed by gm_destroy. Between
+ * gm_load_begin / gm_load_views_begin and the commit: GM_ESTATE. A stored state whose escape lists
+ * disagree with its cells (a piece's escape bytes against its list's count, the pool extent against the
+ * stripe's region, every entry a column < band that holds an escape byte), or a view entry with an id
+ * outside [1, n]: GM_ESTATE, nothing written to the caller's arrays. */
+int gm_digest(gm_ctx *ctx, uint64_t sums[2], uint64_t *rows, uint64_t *nodes);
+/* Start recording from the next tick, for ticks < tmax (0 < tmax <= 32767, else GM_EINVAL; a second
+ * call: GM_ESTATE): after each such tick t the digest kernels run on the stream that ran the tick,
+ * behind its last kernel (inside the span gm_last_kernel_ms reports), and write sums into row t of a
+ * device array [tmax][2] -- no host wait, no copy. Row t holds what gm_digest would return if called
+ * right after that gm_tick, before any gm_set_failed that follows it. FAITHFUL: GM_EUNSUPPORTED. SCALED
+ * column shards: GM_EUNSUPPORTED (their targets are settled by deferred draw rounds, after the point
+ * where a stream-ordered reducer could run; gm_digest on demand serves them). PARTIAL row shards record
+ * their own nodes; the shards' traces add up. While recording is off a tick gains no kernel, no
+ * allocation and no copy. Recording does not depend on gm_keep_events; loads are allowed while
+ * recording (a tick that did not run leaves its row 0). */
+int gm_digest_record(gm_ctx *ctx, int32_t tmax);
+/* out[t][2] = sums recorded after tick i, for i < t <= tmax (t <= 0 or t > tmax: GM_EINVAL). A tick
+ * before recording began, or one that never ran, is {0, 0}. GM_ESTATE before gm_digest_record, and when
+ * a recorded tick raised the status word (an inconsistent stored state, as gm_digest). */
+int gm_digest_trace(gm_ctx *ctx, int32_t t, uint64_t *out);
 
 /* Render the membership lists of every node in the parity dump format
  * ("t i inited inGroup bFailed heartbeat n id:hb:ts ...\n" per node). */

@@ -20,6 +20,7 @@
 #   mix_sc     SQ instruction mix / wave-cycle split of S-C (one --pmc pass) -> $O/mix_sc/
 #   faithful   ./Application on the three testcases + N = 70, timed -> $O/faithful_wall.txt
 #   census     scripts/census_cost.py: gm_census at S-A (cost, self-check)  -> $O/census_cost.json
+#   digest     scripts/digest_cost.py: gm_digest at S-A and S-C (cost, full-size trace comparisons) -> $O/digest_cost.json
 #   viewcensus scripts/view_census_cost.py: gm_view_census at S-C (cost, self-check) -> $O/view_census_cost.json
 #   viewdetect scripts/view_detect_cost.py: the PARTIAL detection recorder at S-C (cost, self-check) -> $O/view_detect_cost.json
 #   readrows   scripts/read_cost.py: gm_read_rows at S-A beside gm_read_table (cost, self-check) -> $O/read_cost.json
@@ -75,6 +76,7 @@ run_step() {
                   echo -n "$c "; { time timeout -k 10 60 ./Application testcases/$c.conf > /dev/null; } 2>&1 || exit 1
                 done ) > $O/faithful_wall.txt 2>&1 ;;
     census) timeout -k 10 420 python -u scripts/census_cost.py --out $O/census_cost.json ${CENSUS_ARGS:-} > $O/census_cost.txt 2> $O/census_cost.err ;;
+    digest) timeout -k 10 900 python -u scripts/digest_cost.py --out $O/digest_cost.json ${DIGEST_ARGS:-} > $O/digest_cost.txt 2> $O/digest_cost.err ;;
     viewcensus) timeout -k 10 900 python -u scripts/view_census_cost.py --out $O/view_census_cost.json ${VIEWCENSUS_ARGS:-} > $O/view_census_cost.txt 2> $O/view_census_cost.err ;;
     viewdetect) timeout -k 10 600 python -u scripts/view_detect_cost.py --out $O/view_detect_cost.json ${VIEWDETECT_ARGS:-} > $O/view_detect_cost.txt 2> $O/view_detect_cost.err ;;
     readrows) timeout -k 10 540 python -u scripts/read_cost.py --out $O/read_cost.json ${READROWS_ARGS:-} > $O/read_cost.txt 2> $O/read_cost.err ;;
