@@ -14,6 +14,7 @@ KOBJS := $(PKG)/build/gm_faithful.o $(PKG)/build/gm_scaled.o $(PKG)/build/gm_ban
          $(PKG)/build/gm_partial.o $(PKG)/build/gm_partial_xchg.o $(PKG)/build/gm_detect.o \
          $(PKG)/build/gm_load.o $(PKG)/build/gm_census.o $(PKG)/build/gm_view_census.o $(PKG)/build/gm_read.o \
          $(PKG)/build/gm_load_views.o $(PKG)/build/gm_view_detect.o $(PKG)/build/gm_digest.o \
+         $(PKG)/build/gm_view_reach.o \
          $(PKG)/build/gm_host.o $(PKG)/build/gm_host_faithful.o $(PKG)/build/gm_host_batch.o $(PKG)/build/gm_host_scaled.o \
          $(PKG)/build/gm_host_shard.o $(PKG)/build/gm_host_partial.o $(PKG)/build/gm_host_events.o \
          $(PKG)/build/gm_host_read.o $(PKG)/build/gm_host_stage.o $(PKG)/build/gm_host_load.o \

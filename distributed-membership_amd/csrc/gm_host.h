@@ -9,7 +9,7 @@
 //   gm_host_partial.hip   PARTIAL: state, tick, the row shards' exchange
 //   gm_host_events.hip    event drains, detection recorder, msgcount
 //   gm_host_view_detect.hip  PARTIAL detection recorder (gm_view_detect_*)
-//   gm_host_read.hip      read-backs: rows, tables, views, nodes, targets, the censuses
+//   gm_host_read.hip      read-backs: rows, tables, views, nodes, targets, the censuses, view reachability
 //   gm_host_digest.hip    state digests: gm_digest, the per-tick recorder (gm_digest_record / _trace)
 //   gm_host_stage.hip     the staged block of gm_read_rows and the loads: size, timing, stats
 //   gm_host_load.hip      gm_load_*, gm_load_views_*: one block loop, one commit tail
@@ -62,6 +62,13 @@ struct gm_view_census_scratch {
   uint8_t *blob = nullptr;
   gm_view_rec *rec = nullptr;
   int64_t nfailed = -1;              // gm_ctx.nfailed when the bitmap was last built (-1: never)
+};
+
+// PARTIAL view-graph reachability (gm_view_reach): device scratch, one block allocated on first use. blob: the
+// per-node words seen, front, next [n] (8 bytes each), the counts [GM_VIEW_HOPS][GM_REACH_SOURCES], the
+// sources [GM_REACH_SOURCES] and the kernels' status word
+struct gm_view_reach_scratch {
+  uint8_t *blob = nullptr;
 };
 
 // PARTIAL detection recorder (gm_view_detect_record; tmax 0 = off), all on the device and allocated
@@ -212,6 +219,7 @@ struct gm_ctx {
   PState p{};  // PARTIAL
   gm_partial_host ph;
   gm_view_census_scratch vc;
+  gm_view_reach_scratch vr;
   gm_view_detect_state vdet;
   gm_load_stage vl;
   gm_shard_exchange xch;  // SCALED column shards, PARTIAL row shards

@@ -433,3 +433,77 @@ extern "C" int gm_view_census(gm_ctx *c, gm_view_rec *out, uint64_t *hist, uint6
   if (sizes) HIPCHECK(ctx_memcpy(c, sizes, d_sizes, sizes_bytes, hipMemcpyDeviceToHost));
   return GM_OK;
 }
+
+// PARTIAL: reachability in the view graph as of the last tick (gm_view_reach.hip). A read-back with the
+// census's preamble; it writes nothing but its own scratch. One launch pair per level on the context's
+// stream; the level's row of counts comes back before the next one is enqueued, and the walk stops at an
+// empty level, at max_hops, or once every live source has reached every live node.
+extern "C" int gm_view_reach(gm_ctx *c, const int32_t *sources, int32_t nsrc, int32_t dir, int32_t max_hops,
+                             uint64_t *counts, uint64_t *seen, int64_t info[4]) {
+  if (!c) return GM_EINVAL;
+  if (c->cfg.mode != GM_MODE_PARTIAL) return GM_EUNSUPPORTED;
+  const PState &p = c->p;
+  if (c->cfg.shard_count > 1 || p.nloc != p.n) return GM_EUNSUPPORTED;  // no frontier exchange between row shards
+  if (!sources || (!counts && !info) || nsrc < 1 || nsrc > GM_REACH_SOURCES || max_hops < 1 || max_hops > GM_VIEW_HOPS ||
+      (dir != GM_REACH_OUT && dir != GM_REACH_IN))
+    return GM_EINVAL;
+  for (int k = 0; k < nsrc; k++)
+    if (sources[k] < 0 || sources[k] >= p.n) return GM_EINVAL;
+  if (c->vl.loading) return GM_ESTATE;  // between gm_load_views_begin and the commit
+  if (c->latched != GM_OK) return c->latched;
+  if (c->xch.stream) HIPCHECK(hipStreamSynchronize(c->xch.stream));  // one rank forced into the sharded tick
+  TRY(check_err(c));  // waits for the stream
+  const size_t n = (size_t)p.n, words = sizeof(uint64_t) * n;
+  const size_t row_bytes = sizeof(uint64_t) * GM_REACH_SOURCES, counts_bytes = row_bytes * GM_VIEW_HOPS;
+  const size_t src_off = 3 * words + counts_bytes, status_off = src_off + sizeof(int32_t) * GM_REACH_SOURCES;
+  if (!c->vr.blob) TRY(dalloc(c, &c->vr.blob, status_off + sizeof(uint64_t)));
+  uint64_t *d_seen = (uint64_t *)c->vr.blob, *d_front = d_seen + n, *d_next = d_front + n, *d_counts = d_next + n;
+  int32_t *d_src = (int32_t *)(c->vr.blob + src_off);
+  uint32_t *d_status = (uint32_t *)(c->vr.blob + status_off);
+  HIPCHECK(ctx_memset(c, c->vr.blob, 0, status_off + sizeof(uint64_t)));
+  HIPCHECK(ctx_memcpy(c, d_src, sources, sizeof(int32_t) * nsrc, hipMemcpyHostToDevice));
+  HIPCHECK(gm_launch_view_reach_seed(p, d_src, nsrc, d_seen, d_front, d_counts, c->stream));
+  std::vector<uint64_t> cnt((size_t)GM_VIEW_HOPS * GM_REACH_SOURCES, 0);
+  HIPCHECK(ctx_memcpy(c, cnt.data(), d_counts, row_bytes, hipMemcpyDeviceToHost));
+  // the device's crash flags are failed_h's (gm_set_failed, the load's commit), so nfailed counts them
+  const uint64_t live = (uint64_t)(p.n - c->nfailed);
+  uint64_t full = 0, reached[GM_REACH_SOURCES];
+  int64_t live_sources = 0;
+  for (int k = 0; k < GM_REACH_SOURCES; k++) {
+    reached[k] = cnt[k];
+    if (cnt[k]) full |= 1ull << k;
+    live_sources += cnt[k] != 0;
+  }
+  for (int h = 1; h < max_hops && full; h++) {
+    bool all = true;  // every live source has reached every live node: the next level is empty
+    for (int k = 0; k < nsrc; k++) all = all && (!((full >> k) & 1) || reached[k] == live);
+    if (all) break;
+    HIPCHECK(gm_launch_view_reach_hop(p, c->t - 1, dir, h, nsrc, full, d_seen, d_front, d_next, d_counts, d_status,
+                                      c->stream));
+    uint64_t *row = cnt.data() + (size_t)h * GM_REACH_SOURCES;
+    HIPCHECK(ctx_memcpy(c, row, d_counts + (size_t)h * GM_REACH_SOURCES, row_bytes, hipMemcpyDeviceToHost));
+    bool any = false;
+    for (int k = 0; k < GM_REACH_SOURCES; k++) {
+      reached[k] += row[k];
+      any = any || row[k];
+    }
+    if (!any) break;
+  }
+  // nothing is handed out before the walk's checks pass
+  TRY(kernel_status(c, d_status, GM_ESTATE, "gm_view_reach: a stored view names an id outside [1, n] (flags 0x%x)"));
+  int hops = 0;
+  for (int h = 0; h < max_hops; h++)
+    for (int k = 0; k < GM_REACH_SOURCES; k++)
+      if (cnt[(size_t)h * GM_REACH_SOURCES + k]) hops = h;
+  bool last = false;
+  for (int k = 0; k < GM_REACH_SOURCES; k++) last = last || cnt[(size_t)(max_hops - 1) * GM_REACH_SOURCES + k];
+  if (seen) HIPCHECK(ctx_memcpy(c, seen, d_seen, words, hipMemcpyDeviceToHost));
+  if (counts) memcpy(counts, cnt.data(), counts_bytes);
+  if (info) {
+    info[0] = (int64_t)live;
+    info[1] = hops;
+    info[2] = last ? 1 : 0;
+    info[3] = live_sources;
+  }
+  return GM_OK;
+}

@@ -100,7 +100,7 @@ struct PState {
 #define GM_PL_EINBOX 0x10000u  // more lists for one receiver than its inbox holds
 
 // host launch wrappers (gm_partial.hip; unpack and pack: gm_partial_xchg.hip; gm_view_census.hip,
-// gm_view_detect.hip, gm_load_views.hip)
+// gm_view_reach.hip, gm_view_detect.hip, gm_load_views.hip)
 hipError_t gm_launch_partial_init(const PState &s, int t0, uint64_t init_seed, hipStream_t st);
 hipError_t gm_launch_partial_unpack(const PState &s, int t, int base, int nrecv, hipStream_t st);
 hipError_t gm_launch_partial_pack(const PState &s, int t, int c, hipStream_t st);
@@ -109,6 +109,11 @@ hipError_t gm_launch_partial_reset(const PState &s, hipStream_t st);
 hipError_t gm_launch_partial_chunk(const PState &s, int t, const uint32_t *mtraw, int c, hipStream_t st);
 hipError_t gm_launch_view_census(const PState &s, const uint32_t *cls, void *acc, gm_view_rec *rec, uint64_t *hist,
                                  uint64_t *sizes, uint32_t *status, int T, hipStream_t st);
+hipError_t gm_launch_view_reach_seed(const PState &s, const int32_t *src, int nsrc, uint64_t *seen, uint64_t *front,
+                                     uint64_t *counts, hipStream_t st);
+hipError_t gm_launch_view_reach_hop(const PState &s, int T, int dir, int h, int nsrc, uint64_t full, uint64_t *seen,
+                                    uint64_t *front, uint64_t *next, uint64_t *counts, uint32_t *status,
+                                    hipStream_t st);
 hipError_t gm_launch_view_detect(const PState &s, const uint32_t *cls, gm_view_detect_rec *rec, uint64_t *tl_row,
                                  uint32_t *status, int t, hipStream_t st);
 hipError_t gm_launch_view_load_check(const PState &s, int t, int cnt, const uint64_t *stage, uint32_t *status,

@@ -13,4 +13,5 @@ from .app import Application, BatchApplication, Params, format_msgcount, log_add
 from .detect import merge_view_detect_shards, summarize, summarize_view_detect  # noqa: F401
 from .census import merge_shards, summarize_census  # noqa: F401
 from .views import merge_view_shards, summarize_views  # noqa: F401
+from .reach import summarize_reach  # noqa: F401
 from . import digest, state  # noqa: F401

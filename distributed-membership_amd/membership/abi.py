@@ -68,6 +68,11 @@ GM_VIEW_AGES, GM_VIEW_SIZES = 32, 33
 VIEW_DTYPE = np.dtype([("hb_min", "<i4"), ("hb_max", "<i4"), ("holders", "<u4"), ("stale", "<u4"), ("hb_sum", "<u8")])
 assert VIEW_DTYPE.itemsize == ctypes.sizeof(GmViewRec) == 24
 
+# gm_view_reach: levels and sources of one walk, the two directions
+GM_VIEW_HOPS, GM_REACH_SOURCES = 64, 64
+GM_REACH_OUT, GM_REACH_IN = 0, 1
+
+
 class GmViewDetectRec(ctypes.Structure):
     _fields_ = [("fail_tick", ctypes.c_int32), ("first_removed", ctypes.c_int32), ("last_removed", ctypes.c_int32),
                 ("removals", ctypes.c_uint32), ("false_removals", ctypes.c_uint32), ("last_held", ctypes.c_int32),
@@ -125,6 +130,7 @@ SIGNATURES = {
     "gm_load_commit": _load4, "gm_load_stats": [_ctx, _P(_f64)],
     "gm_census": [_ctx, _P(GmCensusRec), _P(_u64)],
     "gm_view_census": [_ctx, _P(GmViewRec), _P(_u64), _P(_u64)],
+    "gm_view_reach": [_ctx, _P(_i32), _i32, _i32, _i32, _P(_u64), _P(_u64), _P(_i64)],
     "gm_view_detect_record": [_ctx, _i32], "gm_view_detect": [_ctx, _P(GmViewDetectRec)],
     "gm_view_detect_timeline": [_ctx, _i32, _P(_u64)],
     "gm_read_rows": [_ctx, _i32, _i32, _P(_i32), _P(_i32)], "gm_read_rows_stats": [_ctx, _P(_f64)],
@@ -366,6 +372,28 @@ class Simulator:
         self._call("gm_view_census", self.h, rec.ctypes.data_as(ctypes.POINTER(GmViewRec)) if records else None,
                    _ptr(hist, ctypes.c_uint64), _ptr(sizes, ctypes.c_uint64))
         return rec, hist, sizes
+
+    def view_reach(self, sources, direction="out", max_hops=None, seen=False):
+        """PARTIAL, one context: breadth-first walks of the view graph as of the last tick, on the device
+        (gm_view_reach). The graph: the live nodes, an edge i -> j where the stored view of i names j.
+        sources: up to GM_REACH_SOURCES node indices, walked independently; direction "out": the paths
+        source -> x (who hears from the source), "in": the paths x -> source (whose gossip reaches it);
+        max_hops (default GM_VIEW_HOPS): levels 0 .. max_hops - 1 are walked. Returns a dict: counts
+        uint64 [GM_VIEW_HOPS, nsrc], counts[h, k] = live nodes at distance h of source k (a crashed
+        source's column is 0); live, the live nodes; hops, the last non-empty level; stopped, True when
+        the walk ended because of max_hops; live_sources; seen uint64 [n], bit k set where source k's
+        distance is below max_hops, or None when not asked for."""
+        if direction not in ("out", "in"):
+            raise ValueError("view_reach: direction is 'out' or 'in'")
+        src = np.ascontiguousarray(np.asarray(sources, dtype=np.int32).reshape(-1))
+        counts = np.zeros((GM_VIEW_HOPS, GM_REACH_SOURCES), dtype=np.uint64)
+        words = np.zeros(self.n, dtype=np.uint64) if seen else None
+        info = (ctypes.c_int64 * 4)()
+        self._call("gm_view_reach", self.h, _ptr(src), len(src), GM_REACH_OUT if direction == "out" else GM_REACH_IN,
+                   GM_VIEW_HOPS if max_hops is None else int(max_hops), _ptr(counts, ctypes.c_uint64),
+                   _ptr(words, ctypes.c_uint64) if seen else None, info)
+        return {"counts": np.ascontiguousarray(counts[:, :len(src)]), "live": int(info[0]), "hops": int(info[1]),
+                "stopped": bool(info[2]), "live_sources": int(info[3]), "seen": words}
 
     def view_detect_record(self, tmax):
         """PARTIAL: record how crashed nodes fade from the views, from the next tick on, for ticks < tmax

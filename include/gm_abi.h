@@ -390,6 +390,47 @@ typedef struct gm_view_rec {      /* 24 bytes, one per subject node of the CLUST
  * age >= GM_VIEW_AGES (the sweep removes at age 20) -- : GM_ESTATE, no output written. */
 int gm_view_census(gm_ctx *ctx, gm_view_rec *out, uint64_t *hist, uint64_t *sizes);
 
+/* ---- PARTIAL: reachability in the view graph, walked on the device (the views are not copied to the
+ * host). A partial-view protocol is correct only while its overlay stays connected; the census shows
+ * degrees, this shows paths. The definition is normative.
+ *
+ * The view graph G_T is taken at the last tick run, T = gm_time - 1 (after create or a view load: as
+ * created / loaded). Vertices: the nodes whose crash flag is 0, as gm_read_nodes reports it (the flags
+ * gm_view_census uses for observers). Edges: i -> j iff i and j are both vertices, i != j, and the
+ * stored view of i (what gm_read_views returns) holds an entry with id j + 1. An entry naming a crashed
+ * node, or the node itself, is not an edge; a crashed node's frozen view contributes nothing. Gossip
+ * travels along edges: a node sends its list to targets drawn from its own view.
+ *
+ * Up to GM_REACH_SOURCES sources s_0 .. s_{nsrc-1} are walked independently (bit k of a 64-bit word per
+ * node belongs to source k):
+ *   GM_REACH_OUT  d_k(x) = length of the shortest path s_k -> x ("who can hear from s_k")
+ *   GM_REACH_IN   d_k(x) = length of the shortest path x -> s_k ("whose gossip can reach s_k")
+ * counts[GM_VIEW_HOPS][GM_REACH_SOURCES]: counts[h][k] = vertices x with d_k(x) == h, for h < max_hops;
+ * counts[0][k] is 1 for a live source and 0 for a crashed one, whose whole column is 0; rows >= max_hops
+ * and columns >= nsrc are 0. seen[n] (may be NULL): bit k of seen[x] is set iff d_k(x) < max_hops;
+ * crashed nodes are 0. info = {live vertices, hops = the largest h with a non-zero row of counts,
+ * stopped = 1 iff row max_hops - 1 is non-zero (the walk ended because of max_hops; 0: a level came up
+ * empty first), live sources}. counts and info may not both be NULL. 1 <= max_hops <= GM_VIEW_HOPS;
+ * max_hops = 1 returns the sources only, so calls with max_hops = 1, 2, 3, .. yield per-node distances
+ * from seen. The same node may be named twice; its bits then behave identically.
+ *
+ * GM_EINVAL: nsrc outside 1..GM_REACH_SOURCES, a source outside [0, n), dir not 0 / 1, max_hops out of
+ * range, sources NULL, counts and info both NULL. FAITHFUL / SCALED: GM_EUNSUPPORTED. A PARTIAL row
+ * shard (shard_count > 1): GM_EUNSUPPORTED -- there is no frontier exchange between shards; a sharded
+ * run is moved into one context first (membership.state.join_rows). Between gm_load_views_begin and
+ * the commit: GM_ESTATE. A stored entry the walk meets whose id is outside [1, n]: GM_ESTATE, nothing
+ * written to the caller's arrays. The call is a read-back: it reports a latched device error, waits for
+ * the enqueued ticks, and writes nothing a tick or another read observes. One launch pair per hop on the
+ * context's stream; the host reads the hop's row of counts (512 bytes) to decide whether to go on. Its
+ * device scratch is one block, allocated by the first call and freed by gm_destroy: the per-node words
+ * seen, front and next (3 x 8 n bytes) plus the counts (32 KiB), the sources and a status word. */
+#define GM_VIEW_HOPS 64
+#define GM_REACH_SOURCES 64
+#define GM_REACH_OUT 0
+#define GM_REACH_IN 1
+int gm_view_reach(gm_ctx *ctx, const int32_t *sources, int32_t nsrc, int32_t dir, int32_t max_hops,
+                  uint64_t *counts, uint64_t *seen, int64_t info[4]);
+
 /* ---- PARTIAL: how crashed nodes fade from the views, recorded on the device. gm_detect_record stays
  * unsupported in this mode: a full view evicts a crashed node's stale entry in favour of fresher ones
  * long before TREMOVE, so REMOVED records are nearly absent and JOINED records are churn. What a
