@@ -14,11 +14,12 @@ KOBJS := $(PKG)/build/gm_faithful.o $(PKG)/build/gm_scaled.o $(PKG)/build/gm_ban
          $(PKG)/build/gm_partial.o $(PKG)/build/gm_partial_xchg.o $(PKG)/build/gm_detect.o \
          $(PKG)/build/gm_load.o $(PKG)/build/gm_census.o $(PKG)/build/gm_view_census.o $(PKG)/build/gm_read.o \
          $(PKG)/build/gm_load_views.o $(PKG)/build/gm_view_detect.o $(PKG)/build/gm_digest.o \
-         $(PKG)/build/gm_view_reach.o \
+         $(PKG)/build/gm_view_reach.o $(PKG)/build/gm_view_reach_shard.o \
          $(PKG)/build/gm_host.o $(PKG)/build/gm_host_faithful.o $(PKG)/build/gm_host_batch.o $(PKG)/build/gm_host_scaled.o \
          $(PKG)/build/gm_host_shard.o $(PKG)/build/gm_host_partial.o $(PKG)/build/gm_host_events.o \
          $(PKG)/build/gm_host_read.o $(PKG)/build/gm_host_stage.o $(PKG)/build/gm_host_load.o \
-         $(PKG)/build/gm_host_view_detect.o $(PKG)/build/gm_host_digest.o
+         $(PKG)/build/gm_host_view_detect.o $(PKG)/build/gm_host_digest.o \
+         $(PKG)/build/gm_host_view_reach.o
 HDRS := include/gm_abi.h $(CSRC)/gm_device.h $(CSRC)/gm_faithful.h $(CSRC)/gm_scaled.h $(CSRC)/gm_partial.h \
         $(CSRC)/gm_partial_node.h $(CSRC)/gm_host.h $(CSRC)/gm_band.h $(CSRC)/gm_select.h $(CSRC)/gm_digest.h
 # kernel files compiled as part of another unit (gm_band.hip, gm_draw.hip include them)

@@ -10,6 +10,7 @@
 //   gm_host_events.hip    event drains, detection recorder, msgcount
 //   gm_host_view_detect.hip  PARTIAL detection recorder (gm_view_detect_*)
 //   gm_host_read.hip      read-backs: rows, tables, views, nodes, targets, the censuses, view reachability
+//   gm_host_view_reach.hip   view reachability across row shards: the group walk, gm_view_reach_loopback
 //   gm_host_digest.hip    state digests: gm_digest, the per-tick recorder (gm_digest_record / _trace)
 //   gm_host_stage.hip     the staged block of gm_read_rows and the loads: size, timing, stats
 //   gm_host_load.hip      gm_load_*, gm_load_views_*: one block loop, one commit tail
@@ -69,6 +70,15 @@ struct gm_view_census_scratch {
 // sources [GM_REACH_SOURCES] and the kernels' status word
 struct gm_view_reach_scratch {
   uint8_t *blob = nullptr;
+};
+
+// The walk across row shards (gm_view_reach with a communicator, gm_view_reach_loopback): a member's device
+// scratch, one block allocated by the first sharded walk (gm_host_view_reach.hip carves it): the slices seen,
+// front and next [nloc], the cluster-wide words wide [n], the receive area, the counts, the status word and
+// the sources. agree: the device words of an RCCL rank's agreement before the first level
+struct gm_view_reach_shard_scratch {
+  uint8_t *blob = nullptr;
+  uint64_t *agree = nullptr;
 };
 
 // PARTIAL detection recorder (gm_view_detect_record; tmax 0 = off), all on the device and allocated
@@ -220,6 +230,7 @@ struct gm_ctx {
   gm_partial_host ph;
   gm_view_census_scratch vc;
   gm_view_reach_scratch vr;
+  gm_view_reach_shard_scratch vrs;
   gm_view_detect_state vdet;
   gm_load_stage vl;
   gm_shard_exchange xch;  // SCALED column shards, PARTIAL row shards
@@ -361,6 +372,12 @@ int before_tick_events(gm_ctx *c);
 // gm_host_view_detect.hip
 int view_detect_flags(gm_ctx *c);
 int view_detect_tick(gm_ctx *c, int t, hipStream_t st);
+
+// gm_host_view_reach.hip
+int view_reach_args(int n, const int32_t *sources, int nsrc, int dir, int max_hops, const uint64_t *counts,
+                    const int64_t *info);
+int view_reach_group(gm_ctx **g, int G, const int32_t *sources, int nsrc, int dir, int max_hops, uint64_t *counts,
+                     uint64_t *seen, int64_t info[4]);
 
 // gm_host_digest.hip
 int digest_flags(gm_ctx *c);

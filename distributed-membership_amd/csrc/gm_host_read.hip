@@ -435,7 +435,8 @@ extern "C" int gm_view_census(gm_ctx *c, gm_view_rec *out, uint64_t *hist, uint6
 }
 
 // PARTIAL: reachability in the view graph as of the last tick (gm_view_reach.hip). A read-back with the
-// census's preamble; it writes nothing but its own scratch. One launch pair per level on the context's
+// census's preamble; it writes nothing but its own scratch. A context with a communicator walks with its
+// peers (gm_host_view_reach.hip); what follows is the single context. One launch pair per level on the context's
 // stream; the level's row of counts comes back before the next one is enqueued, and the walk stops at an
 // empty level, at max_hops, or once every live source has reached every live node.
 extern "C" int gm_view_reach(gm_ctx *c, const int32_t *sources, int32_t nsrc, int32_t dir, int32_t max_hops,
@@ -443,12 +444,12 @@ extern "C" int gm_view_reach(gm_ctx *c, const int32_t *sources, int32_t nsrc, in
   if (!c) return GM_EINVAL;
   if (c->cfg.mode != GM_MODE_PARTIAL) return GM_EUNSUPPORTED;
   const PState &p = c->p;
-  if (c->cfg.shard_count > 1 || p.nloc != p.n) return GM_EUNSUPPORTED;  // no frontier exchange between row shards
-  if (!sources || (!counts && !info) || nsrc < 1 || nsrc > GM_REACH_SOURCES || max_hops < 1 || max_hops > GM_VIEW_HOPS ||
-      (dir != GM_REACH_OUT && dir != GM_REACH_IN))
-    return GM_EINVAL;
-  for (int k = 0; k < nsrc; k++)
-    if (sources[k] < 0 || sources[k] >= p.n) return GM_EINVAL;
+  if (c->comm) {  // an RCCL rank: the collective walk (gm_host_view_reach.hip), whatever the shard count
+    TRY(view_reach_args(p.n, sources, nsrc, dir, max_hops, counts, info));
+    return view_reach_group(&c, 1, sources, nsrc, dir, max_hops, counts, seen, info);
+  }
+  if (c->cfg.shard_count > 1 || p.nloc != p.n) return GM_EUNSUPPORTED;  // a row shard without peers to exchange with
+  TRY(view_reach_args(p.n, sources, nsrc, dir, max_hops, counts, info));
   if (c->vl.loading) return GM_ESTATE;  // between gm_load_views_begin and the commit
   if (c->latched != GM_OK) return c->latched;
   if (c->xch.stream) HIPCHECK(hipStreamSynchronize(c->xch.stream));  // one rank forced into the sharded tick

@@ -114,6 +114,16 @@ hipError_t gm_launch_view_reach_seed(const PState &s, const int32_t *src, int ns
 hipError_t gm_launch_view_reach_hop(const PState &s, int T, int dir, int h, int nsrc, uint64_t full, uint64_t *seen,
                                     uint64_t *front, uint64_t *next, uint64_t *counts, uint32_t *status,
                                     hipStream_t st);
+// the walk across row shards (gm_view_reach_shard.hip); its status word: an entry's id is outside [1, n]
+#define GM_VRS_EID 1u
+hipError_t gm_launch_view_reach_shard_seed(const PState &s, const int32_t *src, int nsrc, uint64_t *seen,
+                                           uint64_t *front, uint64_t *counts, hipStream_t st);
+hipError_t gm_launch_view_reach_shard_pass(const PState &s, int T, int dir, uint64_t full, const uint64_t *seen,
+                                           const uint64_t *front, uint64_t *next, uint64_t *wide, uint32_t *status,
+                                           hipStream_t st);
+hipError_t gm_launch_view_reach_shard_commit(const PState &s, int h, int nsrc, uint64_t *seen, uint64_t *front,
+                                             uint64_t *prop, const uint64_t *recv, int nrecv, uint64_t *counts,
+                                             hipStream_t st);
 hipError_t gm_launch_view_detect(const PState &s, const uint32_t *cls, gm_view_detect_rec *rec, uint64_t *tl_row,
                                  uint32_t *status, int t, hipStream_t st);
 hipError_t gm_launch_view_load_check(const PState &s, int t, int cnt, const uint64_t *stage, uint32_t *status,

@@ -131,6 +131,7 @@ SIGNATURES = {
     "gm_census": [_ctx, _P(GmCensusRec), _P(_u64)],
     "gm_view_census": [_ctx, _P(GmViewRec), _P(_u64), _P(_u64)],
     "gm_view_reach": [_ctx, _P(_i32), _i32, _i32, _i32, _P(_u64), _P(_u64), _P(_i64)],
+    "gm_view_reach_loopback": [_P(_ctx), _i32, _P(_i32), _i32, _i32, _i32, _P(_u64), _P(_u64), _P(_i64)],
     "gm_view_detect_record": [_ctx, _i32], "gm_view_detect": [_ctx, _P(GmViewDetectRec)],
     "gm_view_detect_timeline": [_ctx, _i32, _P(_u64)],
     "gm_read_rows": [_ctx, _i32, _i32, _P(_i32), _P(_i32)], "gm_read_rows_stats": [_ctx, _P(_f64)],
@@ -374,8 +375,11 @@ class Simulator:
         return rec, hist, sizes
 
     def view_reach(self, sources, direction="out", max_hops=None, seen=False):
-        """PARTIAL, one context: breadth-first walks of the view graph as of the last tick, on the device
-        (gm_view_reach). The graph: the live nodes, an edge i -> j where the stored view of i names j.
+        """PARTIAL: breadth-first walks of the view graph as of the last tick, on the device
+        (gm_view_reach). On one context holding the whole cluster, or on an RCCL rank (comm_init), where
+        the call is a collective every rank makes with the same arguments: counts and the numbers are
+        the cluster's, seen covers the rank's own nodes (shard_layout). Row shards of one device:
+        partial_loopback_view_reach. The graph: the live nodes, an edge i -> j where the stored view of i names j.
         sources: up to GM_REACH_SOURCES node indices, walked independently; direction "out": the paths
         source -> x (who hears from the source), "in": the paths x -> source (whose gossip reaches it);
         max_hops (default GM_VIEW_HOPS): levels 0 .. max_hops - 1 are walked. Returns a dict: counts
@@ -383,17 +387,8 @@ class Simulator:
         source's column is 0); live, the live nodes; hops, the last non-empty level; stopped, True when
         the walk ended because of max_hops; live_sources; seen uint64 [n], bit k set where source k's
         distance is below max_hops, or None when not asked for."""
-        if direction not in ("out", "in"):
-            raise ValueError("view_reach: direction is 'out' or 'in'")
-        src = np.ascontiguousarray(np.asarray(sources, dtype=np.int32).reshape(-1))
-        counts = np.zeros((GM_VIEW_HOPS, GM_REACH_SOURCES), dtype=np.uint64)
-        words = np.zeros(self.n, dtype=np.uint64) if seen else None
-        info = (ctypes.c_int64 * 4)()
-        self._call("gm_view_reach", self.h, _ptr(src), len(src), GM_REACH_OUT if direction == "out" else GM_REACH_IN,
-                   GM_VIEW_HOPS if max_hops is None else int(max_hops), _ptr(counts, ctypes.c_uint64),
-                   _ptr(words, ctypes.c_uint64) if seen else None, info)
-        return {"counts": np.ascontiguousarray(counts[:, :len(src)]), "live": int(info[0]), "hops": int(info[1]),
-                "stopped": bool(info[2]), "live_sources": int(info[3]), "seen": words}
+        rows = self.shard_layout()[1] if self.mode == GM_MODE_PARTIAL else self.n  # an RCCL rank: its own nodes
+        return _view_reach(lambda *a: self._call("gm_view_reach", self.h, *a), rows, sources, direction, max_hops, seen)
 
     def view_detect_record(self, tmax):
         """PARTIAL: record how crashed nodes fade from the views, from the next tick on, for ticks < tmax
@@ -641,6 +636,22 @@ class Simulator:
         self._call("gm_shard_end_tick", self.h)
 
 
+def _view_reach(call, rows, sources, direction, max_hops, seen):
+    """one walk through `call` (the entry point, bound to its contexts), seen over `rows` nodes: the dict
+    Simulator.view_reach documents"""
+    if direction not in ("out", "in"):
+        raise ValueError("view_reach: direction is 'out' or 'in'")
+    src = np.ascontiguousarray(np.asarray(sources, dtype=np.int32).reshape(-1))
+    counts = np.zeros((GM_VIEW_HOPS, GM_REACH_SOURCES), dtype=np.uint64)
+    words = np.zeros(rows, dtype=np.uint64) if seen else None
+    info = (ctypes.c_int64 * 4)()
+    call(_ptr(src), len(src), GM_REACH_OUT if direction == "out" else GM_REACH_IN,
+         GM_VIEW_HOPS if max_hops is None else int(max_hops), _ptr(counts, ctypes.c_uint64),
+         _ptr(words, ctypes.c_uint64) if seen else None, info)
+    return {"counts": np.ascontiguousarray(counts[:, :len(src)]), "live": int(info[0]), "hops": int(info[1]),
+            "stopped": bool(info[2]), "live_sources": int(info[3]), "seen": words}
+
+
 class Batch:
     """R FAITHFUL Simulators of one device ticked together (gm_batch_*): tick() is one tick() of every
     member in one launch set. Every other call stays the member's own, with its usual meaning, also
@@ -708,3 +719,17 @@ def partial_loopback_tick(sims):
     rc = load_library().gm_partial_loopback_tick(arr, len(sims))
     if rc:
         raise GmError(rc, "gm_partial_loopback_tick")
+
+
+def partial_loopback_view_reach(sims, sources, direction="out", max_hops=None, seen=False):
+    """Simulator.view_reach over the G row-shard contexts of one cluster on one device
+    (gm_view_reach_loopback, the frontier exchanged by device copies): the same dict, of the whole
+    cluster; seen uint64 [n], the shards' parts in node order."""
+    arr = (ctypes.c_void_p * len(sims))(*[s.h for s in sims])
+
+    def call(*a):
+        rc = load_library().gm_view_reach_loopback(arr, len(sims), *a)
+        if rc:
+            raise GmError(rc, "gm_view_reach_loopback")
+
+    return _view_reach(call, sims[0].n if sims else 0, sources, direction, max_hops, seen)

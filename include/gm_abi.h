@@ -415,21 +415,55 @@ int gm_view_census(gm_ctx *ctx, gm_view_rec *out, uint64_t *hist, uint64_t *size
  * from seen. The same node may be named twice; its bits then behave identically.
  *
  * GM_EINVAL: nsrc outside 1..GM_REACH_SOURCES, a source outside [0, n), dir not 0 / 1, max_hops out of
- * range, sources NULL, counts and info both NULL. FAITHFUL / SCALED: GM_EUNSUPPORTED. A PARTIAL row
- * shard (shard_count > 1): GM_EUNSUPPORTED -- there is no frontier exchange between shards; a sharded
- * run is moved into one context first (membership.state.join_rows). Between gm_load_views_begin and
- * the commit: GM_ESTATE. A stored entry the walk meets whose id is outside [1, n]: GM_ESTATE, nothing
- * written to the caller's arrays. The call is a read-back: it reports a latched device error, waits for
- * the enqueued ticks, and writes nothing a tick or another read observes. One launch pair per hop on the
- * context's stream; the host reads the hop's row of counts (512 bytes) to decide whether to go on. Its
- * device scratch is one block, allocated by the first call and freed by gm_destroy: the per-node words
- * seen, front and next (3 x 8 n bytes) plus the counts (32 KiB), the sources and a status word. */
+ * range, sources NULL, counts and info both NULL. FAITHFUL / SCALED: GM_EUNSUPPORTED. Between
+ * gm_load_views_begin and the commit: GM_ESTATE. A stored entry the walk meets whose id is outside
+ * [1, n]: GM_ESTATE, nothing written to the caller's arrays. The call is a read-back: it reports a
+ * latched device error, waits for the enqueued ticks, and writes nothing a tick or another read
+ * observes. One launch pair per hop on the context's stream; the host reads the hop's row of counts
+ * (512 bytes) to decide whether to go on. Its device scratch is one block, allocated by the first call
+ * and freed by gm_destroy: the per-node words seen, front and next (3 x 8 n bytes) plus the counts
+ * (32 KiB), the sources and a status word.
+ *
+ * Row shards. The definition does not change: G_T, counts and info are the whole cluster's, whichever
+ * member reports them, and a sharded walk returns exactly what the single-context walk returns on the
+ * joined state. Sources are global node indices and may lie on any shard. The members exchange the
+ * frontier once per level: GM_REACH_IN gathers every member's last level into every member (8 bytes per
+ * node of the other shards received per member and level); GM_REACH_OUT proposes into a cluster-wide
+ * array and sends each member its slice of every other member's (the same size); each level's row of
+ * counts is summed over the group, and every decision to walk another level is taken from summed rows
+ * only. A member's device scratch is one block, allocated by its first sharded walk and freed by
+ * gm_destroy: seen and two more word arrays over its own nodes, one over the cluster's n nodes, a
+ * receive area of one slice of its own size per other member, the counts, the sources, a status word.
+ * The walk reads the views of tick T, the crash flags and nothing of the tick's exchange: it runs on a
+ * group whose exchange is still pending after a view load, and leaves it pending.
+ *
+ *   gm_view_reach on a context with a communicator (gm_comm_init) is a collective: every rank calls it
+ *   with the same arguments. counts and info are the cluster's on every rank; seen has the rank's own
+ *   nloc words (gm_shard_layout). A context of shard_count 1 with a communicator takes this path too,
+ *   with the single-context results. Before the first level the ranks agree, by one MAX all-reduce of
+ *   (h, ~h), on a hash of the sources, nsrc, dir, max_hops, the tick and the crash set; the result of
+ *   each rank's own checks (a latched error, a load in progress) rides along. A disagreement, or a
+ *   failed check on another rank: GM_ESTATE on every rank (the failing rank returns its own code).
+ *   The argument errors above return GM_EINVAL before any collective. After the last level the status
+ *   words are combined, so a bad entry met by one rank is GM_ESTATE on all. A row shard WITHOUT a
+ *   communicator: GM_EUNSUPPORTED (it has nobody to exchange with).
+ *
+ *   gm_view_reach_loopback walks the G row-shard contexts of one cluster living on one device, device
+ *   copies standing in for the collectives: the counterpart of gm_partial_loopback_tick, with its group
+ *   checks (G >= 2, PARTIAL members, ranks 0 .. G - 1 in order, equal t, n, V and chunk count:
+ *   GM_EINVAL otherwise). seen[n] is the whole cluster's, the shards' parts in node order. The argument
+ *   errors of gm_view_reach: GM_EINVAL. A latched error of a member is returned; a member between
+ *   gm_load_views_begin and its commit, or members holding different crash sets: GM_ESTATE. Nothing is
+ *   written to the caller's arrays on any failure. The members' streams are waited for and the walk
+ *   runs on the first member's stream, shard after shard. */
 #define GM_VIEW_HOPS 64
 #define GM_REACH_SOURCES 64
 #define GM_REACH_OUT 0
 #define GM_REACH_IN 1
 int gm_view_reach(gm_ctx *ctx, const int32_t *sources, int32_t nsrc, int32_t dir, int32_t max_hops,
                   uint64_t *counts, uint64_t *seen, int64_t info[4]);
+int gm_view_reach_loopback(gm_ctx **ctxs, int32_t G, const int32_t *sources, int32_t nsrc, int32_t dir,
+                           int32_t max_hops, uint64_t *counts, uint64_t *seen, int64_t info[4]);
 
 /* ---- PARTIAL: how crashed nodes fade from the views, recorded on the device. gm_detect_record stays
  * unsupported in this mode: a full view evicts a crashed node's stale entry in favour of fresher ones
